@@ -24,9 +24,21 @@ A "step" = one pass of the hot path over one batch of B frames resident in HBM:
                            decode of B frames.
   --workload reg1008_4pam (configs[1]).
 Inputs (symbols, AWGN, Bob's x_hat/n_hat/word/syndrome, and for the unfused
-workloads the LAPPRs) are generated on the GPU before the timed region.
+workloads the LAPPRs) are generated on the GPU before the timed region from --seed and
+the rank alone (torch Philox), so two runs with the same arguments decode the same frames.
 
-At N=1 the line also carries
+A plain run sets up, warms up, times the K steps and prints the result line: metric,
+value, ms_per_step, the config and the BER/FER counters of the last step.
+  --dump-outputs DIR  after the timed steps, writes what the last timed step returned to
+                      its caller as DIR/<name>.npy (float64 / float32): final_lappr (the
+                      decoded LAPPRs of a fixed, seeded sample of DUMP_FRAMES frames, one
+                      row per frame, frame numbers in final_lappr_frames), success and
+                      iterations (every frame), and for the fused workload demap_lappr
+                      (the demapped LAPPRs of the same frames).  Ranks > 0 of an N > 1 run
+                      write <name>_rank<r>.npy.
+  --full              adds everything below (off by default).
+
+With --full at N=1 the line also carries
   * roofline  -- the dominant kernel's algorithmic bytes / its hipEvent-timed launch
                  (on its launch stream, inside the timed region), the PMC traffic and
                  VALU issue fraction from profiles/pmc_traffic.json; "bound" names
@@ -62,6 +74,8 @@ SIMDS, CLOCK_HZ = 1024, 2.4e9
 # (k_check<7> under the default schedule, k_fused<7> under split = 2, k_resident<6> / k_iter<6> for
 # configs[1]'s small code) and the fused demap
 PRICED = ("check_d7", "fused_d7", "demap", "resident_d6", "iter_d6")
+# --dump-outputs: the sampled frames (N=64800 doubles each; twice for the fused workload) stay under 64 MB
+DUMP_FRAMES, DUMP_SEED, DUMP_MAX_BYTES = 48, 20240, 64 * 1000 * 1000
 
 # (name, workload, snr, batch, steps, BASELINE.json config it measures, launches timed with hipEvents
 #  in its kernel-stats pass, the one its roofline prices (or None), CPU leg)
@@ -91,9 +105,14 @@ def parse(argv=None):
     p.add_argument("--max-iter", type=int, default=50)
     p.add_argument("--alpha", type=float, default=1.0)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline time budget (0 = skip)")
-    p.add_argument("--no-roofline", action="store_true", help="skip per-kernel event timing")
-    p.add_argument("--no-secondary", action="store_true", help="skip the secondary configs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the roofline (per-kernel event timing, clock pass, copy bandwidth), the "
+                        "CPU baseline and the secondary configs")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU-baseline time budget (0 = skip)")
+    p.add_argument("--no-roofline", action="store_true", help="--full: skip per-kernel event timing")
+    p.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary configs")
     p.add_argument("--graph", type=int, default=0, choices=[0, 1],
                    help="1: replay each step as a captured HIP graph (kernel timings then come from the "
                         "graph's event nodes, i.e. the last replay of the timed region)")
@@ -205,6 +224,9 @@ class StubWork:
     def sync(self):
         pass
 
+    def outputs(self):
+        return {"counters": self.counters().numpy().astype(np.float64)}
+
     def counters(self):
         import torch
 
@@ -290,12 +312,39 @@ class Work:
     def mean_iterations(self):
         return float(self.its.float().mean().item())
 
+    def outputs(self):
+        """What the last step handed its caller: the final LAPPRs (and, fused, the demapped ones) of a
+        fixed, seeded sample of frames, one row per frame, and every frame's success flag and
+        iteration count."""
+        import torch
+
+        fr = np.sort(np.random.default_rng(DUMP_SEED).choice(self.B, min(self.B, DUMP_FRAMES), replace=False))
+        idx = torch.from_numpy(fr).to(self.dev)
+        out = {"final_lappr": self.final.index_select(1, idx).T.contiguous().cpu().numpy(),
+               "final_lappr_frames": fr.astype(np.float64),
+               "success": self.succ[:self.B].cpu().numpy().astype(np.float32),
+               "iterations": self.its[:self.B].cpu().numpy().astype(np.float32)}
+        if self.fused:
+            out["demap_lappr"] = self.lappr.index_select(1, idx).T.contiguous().cpu().numpy()
+        return out
+
     def free(self):
         import torch
 
         for k in ("graph", "batch", "lappr", "final", "succ", "its", "pipe", "dec"):
             setattr(self, k, None)
         torch.cuda.empty_cache()
+
+
+def dump_outputs(path, arrays, rank, world):
+    """DIR/<name>.npy (rank 0) or DIR/<name>_rank<r>.npy, float32 / float64."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} B (> {DUMP_MAX_BYTES})")
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
 
 
 def copy_bandwidth(dev, nbytes=2 << 30, reps=5):
@@ -642,7 +691,7 @@ def main(argv=None):
         torch.cuda.set_device(local)
         w = Work(args.workload, args.snr, args.batch, args.max_iter, args.alpha, args.seed, rank, local)
 
-    prof = not stub and not args.no_roofline
+    prof = not stub and args.full and not args.no_roofline
     graph = bool(args.graph) and not stub
     if graph:
         import qamr
@@ -669,6 +718,8 @@ def main(argv=None):
 
     elapsed = timed_region(w.step, w.sync, args.steps, args.warmup, before, after, device=w.dev)
     local_elapsed = timed_region.local
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w.outputs(), rank, world)
     counters = w.counters()
     dist.all_reduce_sum(counters)
     kstats = kernel_stats() if prof else {}
@@ -690,7 +741,7 @@ def main(argv=None):
 
     out = {
         "metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "steps": args.steps, "warmup": args.warmup, "full": bool(args.full), "ms_per_step": round(1e3 * elapsed / args.steps, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
         "data": "synthetic (GPU-generated AWGN softening frames, torch Philox RNG)" if not stub else "stub",
     }
@@ -706,7 +757,7 @@ def main(argv=None):
         # whole-decode algorithmic bandwidth (SURVEY.md 8(d) B_frame at the iterations actually run)
         B_frame = 16 * w.V + w.C + it_mean * (24 * w.E + 24 * w.V + w.C)
         cpu = None
-        if rank == 0 and world == 1 and args.cpu_seconds > 0:
+        if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
             cpu = cpu_baseline(args, w, args.cpu_seconds)
         snr_, ber, fer, avg_it = SofteningPipeline.summarize(counters.cpu().numpy(), w.pipe.K, w.snr)
         out["config"] = {"workload": args.workload, "code": w.code_name, "V": w.V, "C": w.C, "E": w.E,
@@ -725,7 +776,7 @@ def main(argv=None):
             "ber_fer": {"ber": ber, "fer": fer, "avg_iters_success": avg_it, "frames_counted": int(counters[4])},
             "kernels": kstats,
         })
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             w.free()
             out["secondary"] = secondary(args, rank, local)
     if world > 1:

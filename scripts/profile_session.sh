@@ -8,7 +8,7 @@ export QAMR_NO_CLOCK_PASS=1  # bench.py: no child clock pass under the profiler
 OUT=gpurun_out/prof_${TAG:-r1}
 mkdir -p "$OUT"
 BENCH=${BENCH:-"bench.py"}
-PMC_ARGS=${PMC_ARGS:-"--steps 1 --warmup 0 --cpu-seconds 0 --no-roofline"}
+PMC_ARGS=${PMC_ARGS:-"--full --steps 1 --warmup 0 --cpu-seconds 0 --no-roofline"}
 step() {  # step <name> <secs> <cmd...>
   local name=$1 secs=$2; shift 2
   echo "[$(date +%T)] >>> $name"
@@ -18,7 +18,7 @@ step() {  # step <name> <secs> <cmd...>
   if [ $rc -ne 0 ]; then echo "STOP: $name rc=$rc"; exit $rc; fi
 }
 if [[ ${SKIP_TRACE:-0} != 1 ]]; then
-step trace 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 $BENCH ${TRACE_ARGS:-}
+step trace 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 $BENCH ${TRACE_ARGS:---full}
 fi
 [[ ${SKIP_PMC:-0} == 1 ]] && exit 0
 if [ -n "${PMC_GROUPS:-}" ]; then IFS=';' read -r -a GRPS <<< "$PMC_GROUPS"; else

@@ -136,6 +136,23 @@ def test_bench_world_size_must_match_gpus():
     assert r.returncode != 0 and "must agree" in r.stderr
 
 
+def test_bench_steps_dump_and_full_options(tmp_path):
+    """--steps sets the timed steps (the stub sleeps 2 ms per step), the line carries ms_per_step,
+    --dump-outputs writes float .npy arrays, identical from run to run, and --full is accepted."""
+    import numpy as np
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    out = _bench_line([BENCH, "--gpus", "1", "--steps", "7", "--warmup", "1", "--dump-outputs", str(a)])
+    assert out["steps"] == 7 and out["full"] is False and 2.0 <= out["ms_per_step"] < 50.0
+    assert abs(out["value"] - out["config"]["batch_per_gpu"] * 1e3 / out["ms_per_step"]) / out["value"] < 1e-2
+    out = _bench_line([BENCH, "--gpus", "1", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", str(b)])
+    assert out["steps"] == 2 and out["full"] is True
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["counters.npy"] == sorted(p.name for p in b.iterdir())
+    x, y = np.load(a / "counters.npy"), np.load(b / "counters.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, y) and x.tolist() == [float(v) for v in out["counters"]]
+
+
 # ------------------------------------------------------- RCCL device capability
 def _qamr_dist():
     import sys
