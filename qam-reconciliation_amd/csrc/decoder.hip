@@ -38,8 +38,6 @@
 namespace qr {
 
 enum CheckMode { kFirst = 0, kNormal = 1, kParityOnly = 2 };
-#define QR_STR2(x) #x
-#define QR_STR(x) QR_STR2(x)
 
 // Device-side index checks of the debug build (make -C csrc DEBUG=1 -> qamr/libqamr_debug.so,
 // QR_DEBUG_ASSERT=1; SURVEY.md 5 -- the reference turns bounds checks off, decoder.pyx:181,240,
@@ -606,9 +604,6 @@ __device__ __forceinline__ void var_sweep_body(const VarArgs &a);
 
 template <bool INIT, bool NT>
 __global__ void __launch_bounds__(256) k_var(VarArgs a) {
-#ifdef QR_EXPERIMENT_VAR_VGPR  // register-rule probe builds only: allocate this many VGPRs (e.g. 24)
-    __asm__ volatile("" ::: "v" QR_STR(QR_EXPERIMENT_VAR_VGPR_LAST));
-#endif
     select_range(a);
     if (!INIT && range_narrow(a.sel, a.acount)) {  // kernel-uniform
         var_narrow_sweep(a);
@@ -662,7 +657,7 @@ __device__ __forceinline__ void var_sweep_body(const VarArgs &a) {
 //   * post(t-1) on the fly, its parity (unsat(t-1), t >= 2), c2v(t) (t <= max_it).
 // Per frame the order is the reference's: check(t) -> status(t-1) -> var(t) -> check(t+1);
 // P(max_it + 1) is the final parity sweep.  Used for single-degree-class codes with D <= 10
-// when the split schedules do not pay (knob fused_iter).
+// when the two-stream schedule does not pay (knob fused_iter).
 struct IterArgs {
     const int32_t *checks;
     int64_t n_checks;
@@ -953,38 +948,6 @@ __global__ void __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_e
     else resident_loop<D, false>(a, f, msg, post, tab, wb);
 }
 
-// One launch = the check sweep of one frame half and the variable sweep of the
-// other (they never touch the same frame columns).  The check sweep is VALU heavy
-// and the variable sweep HBM bound: interleaving their workgroups (evenly spread
-// over the 1-D grid, in proportion to their counts) lets the dispatcher co-schedule
-// them on every CU, so the message stream of one hides under the arithmetic of the
-// other.
-// Occupancy floor (amdgpu_waves_per_eu, MI355X, scripts/exp_build.sh): 4 waves/SIMD = 128
-// VGPRs, 5.56 ms per launch vs 5.68 at 5 waves (96 VGPRs); issue-bound on fp64 VALU (the F and
-// B chains evaluated side by side for more ILP: no gain).
-#ifndef QR_FUSED_STRICT_WAVES
-#define QR_FUSED_STRICT_WAVES 4
-#endif
-
-template <int D, int MODE, bool NT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QR_FUSED_STRICT_WAVES, 8)))
-k_fused(CheckArgs ca, VarArgs va, unsigned nb_check, unsigned nb_total) {
-    __shared__ GlibcTablesBP tab;
-    __shared__ double hb[kPackLdsDoubles];
-    const unsigned b = blockIdx.x;
-    const unsigned c0 = (unsigned)(((uint64_t)b * nb_check) / nb_total);
-    const unsigned c1 = (unsigned)(((uint64_t)(b + 1) * nb_check) / nb_total);
-    if (c1 > c0) {  // block-uniform branch
-        if (!frames_block_live(ca.acount, c0 / ca.nbx, ca.g.lft)) return;
-        if (MODE != kParityOnly) stage_glibc_tables(&tab, ca.gglibc);
-        check_block<D, MODE, NT>(ca, c0 % ca.nbx, c0 / ca.nbx, ca.g.per, tab, hb);
-    } else {
-        const unsigned vi = b - c0;
-        if (!frames_block_live(va.acount, vi / va.nbx, va.g.lft)) return;
-        var_block<false, NT>(va, vi % va.nbx, vi / va.nbx);
-    }
-}
-
 // Check degrees above the templated range (2..kMaxTemplDeg) take a runtime-degree kernel
 // with no per-lane arrays, so any degree works (the reference sizes its F/B buffer per
 // check, decoder.pyx:131-141): the forward values F_0..F_{d-3} of the reference's
@@ -1194,13 +1157,12 @@ constexpr int kRepackChunk = kRepackThreads * kRepackPer;
 // disturb the other range's check launch beside them -- 4.0 dB +0.6 % over 512, 32 too few)
 
 struct RepackArgs {
-    int f0, h, ld, pct;  // the range's first column and full width; repack threshold (percent)
-    int64_t E, V, C;
+    int f0, ld, pct;  // the range's first column; repack threshold (percent)
+    int64_t V, C;
     const int32_t *count;  // the range's running-frame count
     int32_t *sel;          // its RangeSel
     int32_t *list;         // active-frame list (absolute columns, list[f0 + p])
     uint8_t *active;
-    double *c2v[2];              // message rows of column sets 0 (the workspace's) and 1
     double *out_post;            // the caller's posterior output (frame f at column f)
     const double *lappr_in;      // the caller's LAPPRs
     const uint8_t *synd_in;      // the caller's syndrome bits
@@ -1434,6 +1396,7 @@ struct DecodeWs {
         int32_t *fid;
     } rs;
     bool repack;
+    size_t base_bytes, set_bytes;  // of the base part; of the work set when the workspace carries it, else 0
 };
 
 // Codes the one-launch-per-iteration schedule (k_iter) can run: one check-degree class of a
@@ -1441,63 +1404,6 @@ struct DecodeWs {
 static bool iter_code(const qr_code *code, int ld) {
     return code->classes.size() == 1 && code->classes[0].degree >= 2 && code->classes[0].degree <= kPackMaxDeg &&
            code->max_dv <= 64 && (size_t)code->E * ld * sizeof(double) <= ((size_t)1 << 30);
-}
-
-static size_t ws_base_bytes(const qr_code *code, int ld, int max_it) {
-    const int64_t rows = (int64_t)(max_it > 0 ? max_it : 0) + 2;  // no int overflow at INT_MAX
-    const size_t msg = align_up((size_t)code->E * ld * sizeof(double), 256);
-    return msg + (iter_code(code, ld) ? msg : 0) + align_up((size_t)ld, 256) +
-           align_up((size_t)rows * ld, 256) + align_up((size_t)code->fb_rows * ld * sizeof(double), 256) +
-           align_up((size_t)ld * sizeof(int32_t), 256) + 256;
-}
-static size_t repack_set_bytes(const qr_code *code, int ld) {
-    return 3 * align_up((size_t)code->V * ld * sizeof(double), 256) + 2 * align_up((size_t)code->C * ld, 256) +
-           align_up((size_t)code->E * ld * sizeof(double), 256) + align_up((size_t)ld * sizeof(int32_t), 256);
-}
-static size_t ws_repack_bytes(const qr_code *code, int ld);  // after g_tune
-static size_t ws_bytes(const qr_code *code, int ld, int max_it) {
-    return ws_base_bytes(code, ld, max_it) + ws_repack_bytes(code, ld);
-}
-
-static DecodeWs carve(const qr_code *code, int ld, int max_it, void *base, size_t ws_size) {
-    DecodeWs w;
-    char *p = (char *)base;
-    const int64_t rows = (int64_t)(max_it > 0 ? max_it : 0) + 2;  // no int overflow at INT_MAX
-    w.c2v = (double *)p;
-    p += align_up((size_t)code->E * ld * sizeof(double), 256);
-    w.c2v2 = nullptr;
-    if (iter_code(code, ld)) {
-        w.c2v2 = (double *)p;
-        p += align_up((size_t)code->E * ld * sizeof(double), 256);
-    }
-    w.active = (uint8_t *)p;
-    p += align_up((size_t)ld, 256);
-    w.unsat = (uint8_t *)p;
-    p += align_up((size_t)rows * ld, 256);
-    w.fb = code->fb_rows ? (double *)p : nullptr;
-    p += align_up((size_t)code->fb_rows * ld * sizeof(double), 256);
-    w.alist = (int32_t *)p;
-    p += align_up((size_t)ld * sizeof(int32_t), 256);
-    w.acount = (int32_t *)p;
-    w.rsel = w.acount + 4;
-    p += 256;
-    const size_t extra = ws_repack_bytes(code, ld);
-    w.repack = extra > 0 && ws_size >= ws_base_bytes(code, ld, max_it) + extra;
-    w.rs = DecodeWs::WorkSet{nullptr, {nullptr, nullptr}, {nullptr, nullptr}, nullptr, nullptr};
-    if (w.repack) {
-        w.rs.post = (double *)p;
-        p += align_up((size_t)code->V * ld * sizeof(double), 256);
-        for (int k = 0; k < 2; ++k) {
-            w.rs.lappr[k] = (double *)p;
-            p += align_up((size_t)code->V * ld * sizeof(double), 256);
-            w.rs.synd[k] = (uint8_t *)p;
-            p += align_up((size_t)code->C * ld, 256);
-        }
-        w.rs.c2v_alt = (double *)p;
-        p += align_up((size_t)code->E * ld * sizeof(double), 256);
-        w.rs.fid = (int32_t *)p;
-    }
-    return w;
 }
 
 // Runtime tuning knobs (qr_tune_set); defaults picked by scripts/tune.py on MI355X.
@@ -1509,13 +1415,44 @@ struct Tuning {
 };
 static Tuning g_tune;
 
+// rows of the unsat flags: one per sweep 0..max_it, plus one (no int overflow at INT_MAX)
+static int64_t unsat_rows(int max_it) { return (int64_t)(max_it > 0 ? max_it : 0) + 2; }
+
+// The decode workspace, laid out here and nowhere else: the base part every schedule needs, then
+// the repack work set.  With a null base the walk only measures (base_bytes, set_bytes; every
+// pointer null); with the caller's buffer of ws_size bytes it yields the pointers.
 // knob repack (default 1): the workspace carries the work set of the repacked ranges when the
 // two-stream schedule can run (ld % 512 == 0) and the set takes at most 1/8 of the device's
-// memory (N=64800, ld=4096: 4.4 GB of 288 GB)
-static size_t ws_repack_bytes(const qr_code *code, int ld) {
-    if (!g_tune.repack.load() || ld % 512) return 0;
-    const size_t b = repack_set_bytes(code, ld);
-    return b <= code->mem_bytes / 8 ? b : 0;
+// memory (N=64800, ld=4096: 4.4 GB of 288 GB); a decode uses it when ws_size has room for it.
+static DecodeWs ws_layout(const qr_code *code, int ld, int max_it, void *base = nullptr, size_t ws_size = 0) {
+    DecodeWs w;
+    Cursor c{(uintptr_t)base};
+    const size_t msgs = (size_t)code->E * ld, posts = (size_t)code->V * ld;
+    w.c2v = c.take<double>(msgs);
+    w.c2v2 = iter_code(code, ld) ? c.take<double>(msgs) : nullptr;
+    w.active = c.take<uint8_t>((size_t)ld);
+    w.unsat = c.take<uint8_t>((size_t)unsat_rows(max_it) * ld);
+    w.fb = code->fb_rows ? c.take<double>((size_t)code->fb_rows * ld) : nullptr;
+    w.alist = c.take<int32_t>((size_t)ld);
+    w.acount = c.take<int32_t>(64);  // the 256-byte count block
+    w.rsel = w.acount + 4;
+    w.base_bytes = c.off;
+    w.rs.post = c.take<double>(posts);
+    for (int k = 0; k < 2; ++k) {
+        w.rs.lappr[k] = c.take<double>(posts);
+        w.rs.synd[k] = c.take<uint8_t>((size_t)code->C * ld);
+    }
+    w.rs.c2v_alt = c.take<double>(msgs);
+    w.rs.fid = c.take<int32_t>((size_t)ld);
+    const size_t set = c.off - w.base_bytes;
+    w.set_bytes = g_tune.repack.load() && ld % 512 == 0 && set <= code->mem_bytes / 8 ? set : 0;
+    w.repack = w.set_bytes > 0 && ws_size >= w.base_bytes + w.set_bytes;
+    if (!w.repack) w.rs = DecodeWs::WorkSet{};
+    return w;
+}
+static size_t ws_bytes(const qr_code *code, int ld, int max_it) {
+    const DecodeWs w = ws_layout(code, ld, max_it);
+    return w.base_bytes + w.set_bytes;
 }
 
 // Frame tile ft (a divisor of ncols, <= ft_req) and nodes per thread.  Small problems (few
@@ -1632,6 +1569,13 @@ struct Plan {
         CASE(14) CASE(15) CASE(16)                                                                           \
         default: handled = false;                                                                            \
     }
+// The same over the packed degrees (2..kPackMaxDeg): the kernels that run only the packed update.
+#define QR_PACKED_DEG_SWITCH(DEG, CASE, handled)                                          \
+    switch (DEG) {                                                                        \
+        CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10)          \
+        default: handled = false;                                                         \
+    }
+static_assert(kPackMaxDeg == 10, "QR_PACKED_DEG_SWITCH ends at CASE(kPackMaxDeg)");
 
 template <int MODE, bool NT>
 static int launch_check_class(const Plan &P, const DegreeClass &cls, const double *post_in, uint8_t *unsat, int f0,
@@ -1716,41 +1660,6 @@ static int launch_var(const Plan &P, int f0, int f1, int32_t *finite = nullptr, 
     return QR_OK;
 }
 
-template <int MODE, bool NT>
-static int launch_fused_nt(const Plan &P, const DegreeClass &cls, uint8_t *unsat, int cf0, int cf1, int vf0, int vf1) {
-    CheckArgs ca = P.check_args(cls, P.post, unsat, cf0, cf1);
-    VarArgs va = P.var_args(vf0, vf1);
-    if (P.compact) {
-        ca.alist = va.alist = P.w.alist;
-        ca.acount = P.count_of(cf0);
-        va.acount = P.count_of(vf0);
-    }
-    const unsigned nbc = ca.nbx * (unsigned)((cf1 - cf0) >> ca.g.lft);
-    const unsigned nbv = va.nbx * (unsigned)((vf1 - vf0) >> va.g.lft);
-    bool handled = true;
-    {
-        ProfScope ps(profiling_on() ? std::string("fused_d") + std::to_string(cls.degree) : std::string(), P.s);
-#define QR_CASE(DD)                                                                           \
-    case DD:                                                                                  \
-        k_fused<DD, MODE, NT><<<nbc + nbv, 256, 0, P.s>>>(ca, va, nbc, nbc + nbv);            \
-        break;
-        QR_DEG_SWITCH(cls.degree, QR_CASE, handled)
-#undef QR_CASE
-    }
-    if (!handled) {  // runtime degree: the two sweeps as plain launches (disjoint frame columns)
-        int rc = launch_check_class<MODE, NT>(P, cls, P.post, unsat, cf0, cf1);
-        return rc ? rc : launch_var<false>(P, vf0, vf1);
-    }
-    QR_LAUNCH_CHECK();
-    return QR_OK;
-}
-
-template <int MODE>
-static int launch_fused(const Plan &P, const DegreeClass &cls, uint8_t *unsat, int cf0, int cf1, int vf0, int vf1) {
-    return P.nt ? launch_fused_nt<MODE, true>(P, cls, unsat, cf0, cf1, vf0, vf1)
-                : launch_fused_nt<MODE, false>(P, cls, unsat, cf0, cf1, vf0, vf1);
-}
-
 static int launch_status(const Plan &P, int f0, int f1, int t, int final_call, int32_t final_iters,
                          const uint8_t *unsat_t) {
     ProfScope ps("status", P.s);
@@ -1799,54 +1708,18 @@ static int run_flat(const Plan &P, int max_it) {
     return QR_OK;
 }
 
-// The same per-frame schedule with the batch split in two frame halves A | B
-// whose sweeps are software-pipelined half an iteration apart:
-//   C_A(1); for t: [V_A(t) | C_B(t)], S_B(t-1), [C_A(t+1) | V_B(t)], S_A(t)
-// C = check sweep (+ parity of the previous posteriors), S = status update,
-// V = variable sweep, [x | y] = one k_fused launch.  Per frame the order
-// C(t) -> S(t-1) -> V(t) -> C(t+1) is exactly that of run_flat.
-static int run_split(const Plan &P, int max_it) {
-    const int ld = P.ld, h = ld / 2;
-    const int A0 = 0, A1 = h, B0 = h, B1 = ld;
-    int big = 0;
-    for (int k = 1; k < (int)P.code->classes.size(); ++k)
-        if (P.code->classes[k].n > P.code->classes[big].n) big = k;
-    const DegreeClass &cls = P.code->classes[big];
-    auto row = [&](int t) { return P.w.unsat + (size_t)t * ld; };
-    int rc;
-    // C_A(1)
-    if ((rc = launch_checks<kFirst>(P, P.post, row(0), A0, A1))) return rc;
-    for (int t = 1; t <= max_it; ++t) {
-        // [V_A(t) | C_B(t)]   (the other degree classes of C_B(t) as plain launches)
-        if (t == 1) {
-            if ((rc = launch_checks<kFirst>(P, P.post, row(0), B0, B1, big))) return rc;
-            if ((rc = launch_fused<kFirst>(P, cls, row(0), B0, B1, A0, A1))) return rc;
-        } else {
-            if ((rc = launch_checks<kNormal>(P, P.post, row(t - 1), B0, B1, big))) return rc;
-            if ((rc = launch_fused<kNormal>(P, cls, row(t - 1), B0, B1, A0, A1))) return rc;
-            if ((rc = launch_status_compact(P, B0, B1, t - 1, row(t - 1)))) return rc;
-        }
-        if (t < max_it) {
-            // [C_A(t+1) | V_B(t)]
-            if ((rc = launch_checks<kNormal>(P, P.post, row(t), A0, A1, big))) return rc;
-            if ((rc = launch_fused<kNormal>(P, cls, row(t), A0, A1, B0, B1))) return rc;
-            if ((rc = launch_status_compact(P, A0, A1, t, row(t)))) return rc;
-        } else {
-            if ((rc = launch_var<false>(P, B0, B1))) return rc;
-        }
-    }
-    return QR_OK;
-}
-
-// run_split's per-frame order with the check and variable sweeps of the two halves
-// as separate kernels on two streams (split = 3): the caller's stream s runs the
-// check sweeps and status updates, s2 the variable sweeps, events order them:
+// The two-stream schedule (split = 3): the batch is cut in two frame halves A | B whose sweeps
+// run half an iteration apart, as separate kernels on two streams.  C = check sweep (+ parity
+// of the previous posteriors), S = status update, V = variable sweep; per frame the order
+// C(t) -> S(t-1) -> V(t) -> C(t+1) is exactly that of run_flat.  The caller's stream s runs
+// the check sweeps and status updates, s2 the variable sweeps, events order them:
 //   s : C_A(1) | [wait vB] C_B(t) S_B(t-1) | [wait vA] C_A(t+1) S_A(t) | ...
 //   s2:        | [wait cA] V_A(t)          | [wait cB] V_B(t)           | ...
 // The variable sweep's 12-VGPR waves fill whatever the 128-VGPR check waves leave of
-// each SIMD and stream their messages under the check sweep's fp64 arithmetic (in
-// the fused launch they take whole check-sized slots instead): 5.15 vs 5.35 ms per
-// half-iteration for the strict arithmetic (MI355X, B=4096).  The variable sweeps are paced
+// each SIMD and stream their messages under the check sweep's fp64 arithmetic (rounds 1-2
+// ran both sweeps as the workgroups of one launch, where the variable workgroups took whole
+// check-sized slots: 5.35 ms per half-iteration against 5.15 here, strict arithmetic,
+// MI355X, B=4096).  The variable sweeps are paced
 // (knob var_pace, workgroups per 128 frames, default 28): unpaced, the sweep saturates HBM for
 // the first ~1.7 ms of the 4.3 ms check launch beside it and the check sweep's gathers stall
 // (VALU issue 0.72 of the launch); paced to stream over the whole check launch, 4.15 ms and
@@ -1874,25 +1747,20 @@ static int side_stream(const qr_code *code, hipStream_t *out) {
     return QR_OK;
 }
 
-// A repack decision point of the range starting at column f0 (full width h), on P.s (the variable
-// stream): one launch, k_repack_rows, decides and, when it repacks, moves the columns and (its
-// last workgroup) updates the range's state.
-static int launch_repack(const Plan &P, int f0, int h) {
-    const qr_code *code = P.code;
+// A repack decision point of the range starting at column f0, on P.s (the variable stream): one
+// launch, k_repack_rows, decides and, when it repacks, moves the columns and (its last
+// workgroup) updates the range's state.
+static int launch_repack(const Plan &P, int f0) {
     RepackArgs r;
     r.f0 = f0;
-    r.h = h;
     r.ld = P.ld;
     r.pct = std::clamp(g_tune.repack_pct.load(), 1, 90);
-    r.E = code->E;
-    r.V = code->V;
-    r.C = code->C;
+    r.V = P.code->V;
+    r.C = P.code->C;
     r.count = P.count_of(f0);
     r.sel = P.w.rsel + (f0 == 0 ? 0 : kSelInts);
     r.list = P.w.alist;
     r.active = P.w.active;
-    r.c2v[0] = P.w.c2v;
-    r.c2v[1] = P.w.rs.c2v_alt;
     r.out_post = P.post;
     r.lappr_in = P.lappr;
     r.synd_in = P.synd;
@@ -1966,7 +1834,7 @@ static int run_split2(const Plan &P, int max_it, bool *finalized) {
     auto var_sweep = [&](int k, int t) {
         const int f0 = k * h;
         if (rp && t < max_it) {
-            if (int rc0 = launch_repack(V, f0, h)) return rc0;
+            if (int rc0 = launch_repack(V, f0)) return rc0;
         }
         return launch_var<false>(V, f0, f0 + h);
     };
@@ -2081,11 +1949,10 @@ static int run_iter(const Plan &P, int max_it) {
     case DD:                                                                            \
         k_iter<DD><<<grid, 256, 0, st[r]>>>(a);                                         \
         break;
-            switch (cls.degree) {
-                QR_CASE(2) QR_CASE(3) QR_CASE(4) QR_CASE(5) QR_CASE(6) QR_CASE(7) QR_CASE(8) QR_CASE(9) QR_CASE(10)
-                default: return set_error(QR_EVALUE, "decode: no fused-iteration kernel for degree %d", cls.degree);
-            }
+            bool handled = true;
+            QR_PACKED_DEG_SWITCH(cls.degree, QR_CASE, handled)
 #undef QR_CASE
+            if (!handled) return set_error(QR_EVALUE, "decode: no fused-iteration kernel for degree %d", cls.degree);
             QR_LAUNCH_CHECK();
         }
     }
@@ -2109,6 +1976,14 @@ static bool resident_code(const qr_code *code) {
            resident_lds(code) + kResStaticLds <= lds_cap;
 }
 
+// The finite clamp's bound (see kPackMaxDeg): 2^e with e = 1000 - (max_it + 2) log2(max_dv + 1),
+// or 0 when e < 1 (no bound: the flag stays clear).  In double, compared before the cast: max_it
+// may be as large as INT_MAX.
+static double finite_bound(int max_it, int max_dv) {
+    const double x = ((double)std::max(max_it, 0) + 2.0) * std::log2((double)max_dv + 1.0);
+    return x > 999.0 ? 0.0 : std::ldexp(1.0, 1000 - (int)std::ceil(x));
+}
+
 static int run_resident(const qr_code *code, int B, int ld, const double *lappr, const uint8_t *synd, int max_it,
                         double *final_post, uint8_t *success, int32_t *iters, int32_t *rsel, hipStream_t s) {
     ResArgs a;
@@ -2129,10 +2004,7 @@ static int run_resident(const qr_code *code, int B, int ld, const double *lappr,
     a.success = success;
     a.iters = iters;
     a.gglibc = code->d_gtab;
-    // the finite clamp's bound, as decode_batch_device's: 2^e, e = 1000 - (max_it + 2) log2(dv_max + 1)
-    const double fin_x = ((double)max_it + 2.0) * std::log2((double)code->max_dv + 1.0);
-    const int fin_e = fin_x > 999.0 ? 0 : 1000 - (int)std::ceil(fin_x);
-    a.fin_bound = fin_e >= 1 ? std::ldexp(1.0, fin_e) : 0.0;
+    a.fin_bound = finite_bound(max_it, code->max_dv);
     a.dv = code->reg_dv >= 1 && code->reg_dv <= 3 && code->E < 65536 ? code->reg_dv : 0;
     const unsigned grid = (unsigned)(8 * ((B + 7) / 8));
     const size_t lds = resident_lds(code);
@@ -2141,11 +2013,10 @@ static int run_resident(const qr_code *code, int B, int ld, const double *lappr,
     case DD:                                                 \
         k_resident<DD><<<grid, kResThreads, lds, s>>>(a);    \
         break;
-    switch (code->classes[0].degree) {
-        QR_CASE(2) QR_CASE(3) QR_CASE(4) QR_CASE(5) QR_CASE(6) QR_CASE(7) QR_CASE(8) QR_CASE(9) QR_CASE(10)
-        default: return set_error(QR_EVALUE, "decode: no frame-resident kernel for degree %d", code->classes[0].degree);
-    }
+    bool handled = true;
+    QR_PACKED_DEG_SWITCH(code->classes[0].degree, QR_CASE, handled)
 #undef QR_CASE
+    if (!handled) return set_error(QR_EVALUE, "decode: no frame-resident kernel for degree %d", code->classes[0].degree);
     QR_LAUNCH_CHECK();
     return QR_OK;
 }
@@ -2157,37 +2028,33 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
         return set_error(QR_EVALUE, "decode: need 0 < B <= ld and ld %% 64 == 0 (B=%d, ld=%d)", B, ld);
     if (!lappr || !synd || !final_post || !success || !iters || !ws_ptr)
         return set_error(QR_EVALUE, "decode: null pointer argument");
-    if (ws_size < ws_base_bytes(code, ld, max_it))
-        return set_error(QR_EVALUE, "decode: workspace too small (%zu < %zu)", ws_size,
-                         ws_base_bytes(code, ld, max_it));
+    const DecodeWs w = ws_layout(code, ld, max_it, ws_ptr, ws_size);
+    if (ws_size < w.base_bytes)
+        return set_error(QR_EVALUE, "decode: workspace too small (%zu < %zu)", ws_size, w.base_bytes);
     DeviceGuard dg(code->device);
     if (max_it > 0 && max_it <= kResMaxIter && resident_code(code))
-        return run_resident(code, B, ld, lappr, synd, max_it, final_post, success, iters,
-                            carve(code, ld, max_it, ws_ptr, ws_size).rsel, s);
-    Plan P{code, B, ld, lappr, synd, final_post, success, iters, carve(code, ld, max_it, ws_ptr, ws_size), g_tune.nt.load() != 0, s};
-    const int64_t rows = (int64_t)(max_it > 0 ? max_it : 0) + 2;  // no int overflow at INT_MAX
+        return run_resident(code, B, ld, lappr, synd, max_it, final_post, success, iters, w.rsel, s);
+    Plan P{code, B, ld, lappr, synd, final_post, success, iters, w, g_tune.nt.load() != 0, s};
     int rc;
-    QR_HIP(hipMemsetAsync(P.w.unsat, 0, (size_t)rows * ld, s));
+    QR_HIP(hipMemsetAsync(P.w.unsat, 0, (size_t)unsat_rows(max_it) * ld, s));
     k_init_status<<<(ld + 255) / 256, 256, 0, s>>>(B, ld, P.w.active, success, iters, P.w.acount + 2, P.w.rsel, ld / 2,
                                                    ld - ld / 2);
     QR_LAUNCH_CHECK();
-    // the strict arithmetic's finite flag: bound 2^e with e = 1000 - (max_it + 2) log2(dv_max + 1)
-    // (in double, clamped before the cast: max_it may be as large as INT_MAX)
-    const double fin_x = ((double)std::max(max_it, 0) + 2.0) * std::log2((double)code->max_dv + 1.0);
-    const int fin_e = fin_x > 999.0 ? 0 : 1000 - (int)std::ceil(fin_x);
-    if (fin_e < 1) QR_HIP(hipMemsetAsync(P.w.acount + 2, 0, sizeof(int32_t), s));
-    // the flag itself is computed by the first variable sweep, which reads every LAPPR anyway
-    int32_t *fin_flag = fin_e >= 1 ? P.w.acount + 2 : nullptr;
+    // the strict arithmetic's finite flag: no bound, never set; otherwise the first variable sweep
+    // computes it, which reads every LAPPR anyway
+    const double fin_bound = finite_bound(max_it, code->max_dv);
+    if (fin_bound == 0.0) QR_HIP(hipMemsetAsync(P.w.acount + 2, 0, sizeof(int32_t), s));
+    int32_t *fin_flag = fin_bound > 0.0 ? P.w.acount + 2 : nullptr;
     // decoder.pyx:400-405: the input itself may already satisfy the syndrome.
     if ((rc = launch_checks<kParityOnly>(P, lappr, P.w.unsat, 0, ld))) return rc;
     if ((rc = launch_status(P, 0, ld, 0, 0, 0, P.w.unsat))) return rc;
     // decoder.pyx:408-421: c2v = 0, first variable sweep.
-    if ((rc = launch_var<true>(P, 0, ld, fin_flag, fin_flag ? std::ldexp(1.0, fin_e) : 0.0))) return rc;
+    if ((rc = launch_var<true>(P, 0, ld, fin_flag, fin_bound))) return rc;
     int max_deg = 0;
     int64_t max_n = 0;
     for (const auto &c : code->classes) max_deg = std::max(max_deg, c.degree), max_n = std::max(max_n, c.n);
-    const int sp = g_tune.split.load();
-    // The split schedules overlap one half's check sweep with the other half's variable sweep;
+    // Knob split: 0 or 1 = lock-step always, 3 (default) = the two-stream schedule where it pays.
+    // It overlaps one half's check sweep with the other half's variable sweep;
     // that pays only when a half's check launch fills the chip on its own (DVB-S2 N=64800:
     // 1013 check blocks x 16 frame tiles at B = 4096).  A small code (configs[1]: reg-(3,6)
     // N=1008, B = 1024: 64 blocks) runs all frames in lock-step instead -- 4.9x the frames/s
@@ -2195,7 +2062,7 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
     const Geom gh = make_geom(ld / 2, g_tune.check_ft.load(), g_tune.check_per.load());
     const int64_t half_blocks = (max_n + (int64_t)gh.per * (256 >> gh.lft) - 1) / ((int64_t)gh.per * (256 >> gh.lft)) *
                                 ((ld / 2) >> gh.lft);
-    const bool split = sp >= 2 && ld % 512 == 0 && max_deg <= 16 && half_blocks >= g_tune.split_min_blocks.load();
+    const bool split = g_tune.split.load() == 3 && ld % 512 == 0 && max_deg <= 16 && half_blocks >= g_tune.split_min_blocks.load();
     const bool iter = !split && max_it > 0 && g_tune.fused_iter.load() && P.w.c2v2;
     if (iter) {
         if ((rc = run_iter(P, max_it))) return rc;
@@ -2210,8 +2077,7 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
         return rc;
     }
     bool finalized = false;
-    if ((rc = !split ? run_flat(P, max_it) : sp == 3 ? run_split2(P, max_it, &finalized) : run_split(P, max_it)))
-        return rc;
+    if ((rc = split ? run_split2(P, max_it, &finalized) : run_flat(P, max_it))) return rc;
     if (finalized) return QR_OK;
     // Check after the last sweep; then every frame still running stops with (0, max).
     const int tf = max_it > 0 ? max_it : 0;
@@ -2458,7 +2324,7 @@ static std::atomic<int> *tune_knob(const char *name) {
 int qr_tune_set(const char *name, int64_t value) {
     std::atomic<int> *k = tune_knob(name);
     if (!k) return set_error(QR_EVALUE, "unknown tuning knob '%s'", name ? name : "");
-    if (value < 0 || value > 4096 || (k == &g_tune.split && value > 3))
+    if (value < 0 || value > 4096 || (k == &g_tune.split && value != 0 && value != 1 && value != 3))
         return set_error(QR_EVALUE, "tuning value out of range");
     k->store((int)value);
     return QR_OK;
@@ -2493,8 +2359,8 @@ int qr_decode_repack_stats(const qr_code *code, int32_t ld, int32_t max_it, cons
                            int32_t *out) {
     if (!code || !ws || !out) return set_error(QR_EVALUE, "null argument");
     if (ld <= 0 || ld % kWave) return set_error(QR_EVALUE, "ld must be a positive multiple of 64");
-    if (ws_size < ws_base_bytes(code, ld, max_it)) return set_error(QR_EVALUE, "workspace too small");
-    const DecodeWs w = carve(code, ld, max_it, const_cast<void *>(ws), ws_size);
+    const DecodeWs w = ws_layout(code, ld, max_it, const_cast<void *>(ws), ws_size);
+    if (ws_size < w.base_bytes) return set_error(QR_EVALUE, "workspace too small");
     int32_t sel[2 * kSelInts];
     DeviceGuard dg(code->device);
     QR_HIP(hipMemcpy(sel, w.rsel, sizeof(sel), hipMemcpyDeviceToHost));
@@ -2519,24 +2385,16 @@ int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, const ui
     if (B <= 0) return set_error(QR_EVALUE, "B must be positive");
     const int ld = (int)align_up((size_t)B, kWave);
     const size_t V = code->V, C = code->C;
-    const size_t n_fm = align_up(V * B * 8, 256), n_fi = align_up(V * ld * 8, 256);
-    const size_t s_fm = align_up(C * B, 256), s_fi = align_up(C * ld, 256);
-    const size_t flags = align_up((size_t)B, 256) + align_up((size_t)B * 4, 256);
     const size_t wsb = ws_bytes(code, ld, max_it);
-    const size_t total = n_fm + 2 * n_fi + s_fm + s_fi + flags + wsb;
     DeviceGuard g(code->device);
     std::lock_guard<std::mutex> lk(code->scratch.mu);
-    int rc = code->scratch.reserve(total);
+    double *d_fm, *d_lappr, *d_final;  // frame-major staging; frame-innermost input and output
+    uint8_t *d_sfm, *d_synd, *d_succ;
+    int32_t *d_it;
+    char *d_ws;
+    int rc = code->scratch.take(&d_fm, V * B, &d_lappr, V * ld, &d_final, V * ld, &d_sfm, C * B, &d_synd, C * ld,
+                                &d_succ, (size_t)B, &d_it, (size_t)B, &d_ws, wsb);
     if (rc) return rc;
-    char *p = (char *)code->scratch.ptr;
-    double *d_fm = (double *)p;          p += n_fm;
-    double *d_lappr = (double *)p;       p += n_fi;
-    double *d_final = (double *)p;       p += n_fi;
-    uint8_t *d_sfm = (uint8_t *)p;       p += s_fm;
-    uint8_t *d_synd = (uint8_t *)p;      p += s_fi;
-    uint8_t *d_succ = (uint8_t *)p;      p += align_up((size_t)B, 256);
-    int32_t *d_it = (int32_t *)p;        p += align_up((size_t)B * 4, 256);
-    void *d_ws = p;
     hipStream_t s = nullptr;
     QR_HIP(hipMemcpyAsync(d_fm, lappr, V * B * 8, hipMemcpyHostToDevice, s));
     QR_HIP(hipMemcpyAsync(d_sfm, synd, C * B, hipMemcpyHostToDevice, s));
@@ -2559,23 +2417,18 @@ static int check_nodes_common(const qr_code *code, const void *vals, size_t val_
     DeviceGuard g(code->device);
     std::lock_guard<std::mutex> lk(code->scratch.mu);
     const size_t C = code->C;
-    const size_t a = align_up(val_bytes, 256), b = align_up(C, 256);
-    int rc = code->scratch.reserve(a + 2 * b);
-    if (rc) return rc;
-    char *p = (char *)code->scratch.ptr;
-    QR_HIP(hipMemcpy(p, vals, val_bytes, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(p + a, synd, C, hipMemcpyHostToDevice));
+    uint8_t *d_vals, *d_synd, *d_ok;
+    if (int rc = code->scratch.take(&d_vals, val_bytes, &d_synd, C, &d_ok, C)) return rc;
+    QR_HIP(hipMemcpy(d_vals, vals, val_bytes, hipMemcpyHostToDevice));
+    QR_HIP(hipMemcpy(d_synd, synd, C, hipMemcpyHostToDevice));
     if (is_word)
-        k_check_word_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var,
-                                                                  (const uint8_t *)p, (const uint8_t *)(p + a),
-                                                                  (uint8_t *)(p + a + b));
+        k_check_word_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var, d_vals, d_synd, d_ok);
     else
         k_check_lappr_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var,
-                                                                   (const double *)p, (const uint8_t *)(p + a),
-                                                                   (uint8_t *)(p + a + b));
+                                                                   (const double *)d_vals, d_synd, d_ok);
     QR_LAUNCH_CHECK();
     std::vector<uint8_t> ok(C);
-    QR_HIP(hipMemcpy(ok.data(), p + a + b, C, hipMemcpyDeviceToHost));
+    QR_HIP(hipMemcpy(ok.data(), d_ok, C, hipMemcpyDeviceToHost));
     uint8_t all = 1;
     for (size_t c = 0; c < C; ++c) {
         if (check_ok) check_ok[c] = ok[c];
@@ -2606,15 +2459,9 @@ int qr_process_var_nodes_host(const qr_code *code, const int64_t *nodes, int64_t
     DeviceGuard g(code->device);
     std::lock_guard<std::mutex> lk(code->scratch.mu);
     const size_t V = code->V, E = code->E;
-    const size_t sn = align_up(n * 8, 256), sv = align_up(V * 8, 256), se = align_up(E * 8, 256);
-    int rc = code->scratch.reserve(sn + 2 * sv + 2 * se);
-    if (rc) return rc;
-    char *p = (char *)code->scratch.ptr;
-    int64_t *d_nodes = (int64_t *)p;   p += sn;
-    double *d_lappr = (double *)p;     p += sv;
-    double *d_upd = (double *)p;       p += sv;
-    double *d_c2v = (double *)p;       p += se;
-    double *d_v2c = (double *)p;
+    int64_t *d_nodes;
+    double *d_lappr, *d_upd, *d_c2v, *d_v2c;
+    if (int rc = code->scratch.take(&d_nodes, n, &d_lappr, V, &d_upd, V, &d_c2v, E, &d_v2c, E)) return rc;
     QR_HIP(hipMemcpy(d_nodes, nodes, n * 8, hipMemcpyHostToDevice));
     QR_HIP(hipMemcpy(d_lappr, lappr, V * 8, hipMemcpyHostToDevice));
     QR_HIP(hipMemcpy(d_upd, updated, V * 8, hipMemcpyHostToDevice));
@@ -2637,14 +2484,10 @@ int qr_process_check_nodes_host(const qr_code *code, const int64_t *nodes, int64
     DeviceGuard g(code->device);
     std::lock_guard<std::mutex> lk(code->scratch.mu);
     const size_t C = code->C, E = code->E;
-    const size_t sn = align_up(n * 8, 256), sc = align_up(C, 256), se = align_up(E * 8, 256);
-    int rc = code->scratch.reserve(sn + sc + 2 * se);
-    if (rc) return rc;
-    char *p = (char *)code->scratch.ptr;
-    int64_t *d_nodes = (int64_t *)p;   p += sn;
-    uint8_t *d_synd = (uint8_t *)p;    p += sc;
-    double *d_c2v = (double *)p;       p += se;
-    double *d_v2c = (double *)p;
+    int64_t *d_nodes;
+    uint8_t *d_synd;
+    double *d_c2v, *d_v2c;
+    if (int rc = code->scratch.take(&d_nodes, n, &d_synd, C, &d_c2v, E, &d_v2c, E)) return rc;
     QR_HIP(hipMemcpy(d_nodes, nodes, n * 8, hipMemcpyHostToDevice));
     QR_HIP(hipMemcpy(d_synd, synd, C, hipMemcpyHostToDevice));
     QR_HIP(hipMemcpy(d_c2v, c2v, E * 8, hipMemcpyHostToDevice));

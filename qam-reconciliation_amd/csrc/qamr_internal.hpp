@@ -45,6 +45,19 @@ constexpr int kWave = 64;
 inline int frame_tile(int ld) { return (ld % 256 == 0) ? 256 : (ld % 128 == 0) ? 128 : 64; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Bump cursor over a device buffer: take<T>(n) is the next n elements of T, 256-byte aligned.
+// With a null base it only measures: every take is null and off counts the bytes walked.
+struct Cursor {
+    uintptr_t base;
+    size_t off = 0;
+    template <typename T>
+    T *take(size_t n) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off += align_up(n * sizeof(T), 256);
+        return p;
+    }
+};
+
 // Device scratch owned by a handle, grown on demand (host-API calls only).
 struct Scratch {
     std::mutex mu;
@@ -52,6 +65,22 @@ struct Scratch {
     size_t bytes = 0;
     int device = 0;
     int reserve(size_t want);  // caller holds mu
+    // take(&p0, n0, &p1, n1, ...): reserve room for n0 elements of *p0's type, n1 of *p1's, ...
+    // (a Cursor walk) and point p0, p1, ... at them (caller holds mu).
+    template <typename... A>
+    int take(A... regions) {
+        Cursor m{0};
+        walk(m, regions...);
+        if (int rc = reserve(m.off)) return rc;
+        Cursor c{(uintptr_t)ptr};
+        walk(c, regions...);
+        return 0;
+    }
+    template <typename T, typename... A>
+    static void walk(Cursor &c, T **p, size_t n, A... rest) {
+        *p = c.take<T>(n);
+        if constexpr (sizeof...(rest) > 0) walk(c, rest...);
+    }
     ~Scratch();
 };
 
@@ -140,7 +169,6 @@ struct qr_code {
     std::vector<DegreeClass> classes;
     int64_t fb_rows = 0;  // rows of the F scratch (sum over runtime-degree classes)
     qr::GlibcTables *d_gtab = nullptr; // strict box-plus: glibc exp/log data (glibc_math.hpp)
-    uint32_t *d_cu_arrivals = nullptr; // per-CU arrival counters of the frame-resident decode (knob res_stagger)
     mutable qr::Scratch scratch;
     // two-stream schedule (decoder.hip run_split2): a second stream for the variable
     // sweeps and the events that order the two; created on first use, guarded by mu

@@ -674,13 +674,8 @@ QR_HD void demap_symbol(const DemapTables& t, const MathTables& mt, const GlibcT
     const double aj = t.a[j];
 #pragma unroll 1
     for (int i = 0; i < M; ++i) {
-#ifdef QR_EXPERIMENT_NO_SEARCH   // cost-breakdown experiments only (scripts/exp_build.sh)
-        const double y = quantile_start(t, i, search_target(t, n, i));
-#else
         const double y = FAST ? g_inv_search_fast(t, mt, n, i) : g_inv_search(t, n, i);
-#endif
         double s = 0;
-#ifndef QR_EXPERIMENT_NO_LLR
         // One loop over all M hypotheses in the reference's summation order (k < j,
         // then p[j], then k > j): lanes of a wave hold different j, so the two
         // j-bounded loops of the reference would run max(j) + max(M-1-j) ≈ 2(M-1)
@@ -693,10 +688,6 @@ QR_HD void demap_symbol(const DemapTables& t, const MathTables& mt, const GlibcT
             const double term = k == j ? t.p[j] : g_exp_full(arg, gt) * t.p[k];
             s += term;
         }
-#else
-        s += t.p[j];
-        s += y * 1e-300;
-#endif
         const double q = t.dF[i] / s;
         int mi = i;
 #pragma unroll

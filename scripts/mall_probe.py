@@ -51,7 +51,7 @@ def main():
                     torch.cuda.synchronize()
                     qamr.profile_enable(False)
                     ks = {}
-                    for k in ("check_d7", "fused_d7", "var", "status"):
+                    for k in ("check_d7", "var", "status"):
                         ms, n = qamr.profile_query(k)
                         if n:
                             ks[k] = ms / n * 1e3

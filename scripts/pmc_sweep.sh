@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=gpurun_out/pmc_sweep; mkdir -p $OUT
 i=0
-for cfg in ${CFGS:-"split=1,nt=1,check_ft=256" "split=1,nt=1,check_ft=64" "split=1,nt=0,check_ft=64" "split=2,nt=1,check_ft=256" "split=2,nt=1,check_ft=64"}; do
+for cfg in ${CFGS:-"split=1,nt=1,check_ft=256" "split=1,nt=1,check_ft=64" "split=1,nt=0,check_ft=64" "split=3,nt=1,check_ft=256" "split=3,nt=1,check_ft=64"}; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     i=$((i+1))
     echo "[$(date +%T)] $cfg $ctr"

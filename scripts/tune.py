@@ -20,8 +20,8 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--grid", default="split=1,2;check_per=2,4,8;nt=0,1")
-    ap.add_argument("--var-grid", default="split=2;var_per=2,4,8;check_ft=128,256")
+    ap.add_argument("--grid", default="split=1,3;check_per=2,4,8;nt=0,1")
+    ap.add_argument("--var-grid", default="var_per=2,4,8;check_ft=128,256")
     args = ap.parse_args()
     import torch
     import qamr
@@ -47,6 +47,7 @@ def main():
             vals.append([int(x) for x in v.split(",")])
         return [dict(zip(keys, c)) for c in itertools.product(*vals)]
 
+    saved = {k: _lib.tune_get(k) for k in ("check_ft", "check_per", "var_ft", "var_per", "nt", "split")}
     ref = None
     results = {}
     configs = parse(args.grid)
@@ -67,10 +68,8 @@ def main():
             torch.cuda.synchronize()
             qamr.profile_enable(False)
             key = json.dumps(cfg, sort_keys=True)
-            rec = results.setdefault(key, {"check_d7": [], "var": [], "wall": [], "fused": []})
+            rec = results.setdefault(key, {"check_d7": [], "var": [], "wall": []})
             rec["wall"].append(wall / args.iters)
-            ms, n = qamr.profile_query("fused_d7")
-            rec["fused"].append(ms / max(n, 1))
             ms, n = qamr.profile_query("check_d7")
             rec["check_d7"].append(ms / max(n, 1))
             ms, n = qamr.profile_query("var")
@@ -82,15 +81,14 @@ def main():
             elif h != ref:
                 print("MISMATCH", cfg, h, ref, flush=True)
             for k in cfg:
-                _lib.tune_set(k, {"check_ft": 256, "check_per": 4, "var_ft": 256, "var_per": 4, "nt": 1,
-                                  "split": 2}[k])
+                _lib.tune_set(k, saved[k])
     rows = []
     for key, rec in results.items():
-        rows.append((min(rec["wall"]), min(rec["check_d7"]), min(rec["var"]), min(rec["fused"]), key))
+        rows.append((min(rec["wall"]), min(rec["check_d7"]), min(rec["var"]), key))
     rows.sort()
-    print(f"{'ms/iter':>8} {'check_d7':>9} {'var':>7} {'fused_d7':>9}  config   (kernel columns: ms per launch)")
-    for w, c, v, fu, k in rows:
-        print(f"{w:8.3f} {c:9.3f} {v:7.3f} {fu:9.3f}  {k}")
+    print(f"{'ms/iter':>8} {'check_d7':>9} {'var':>7}  config   (kernel columns: ms per launch)")
+    for w, c, v, k in rows:
+        print(f"{w:8.3f} {c:9.3f} {v:7.3f}  {k}")
 
 
 if __name__ == "__main__":

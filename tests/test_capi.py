@@ -78,6 +78,25 @@ def _size_mismatch():
     _lib.check(_lib.load().qr_code_create(_lib.ptr(a), _lib.ptr(b), 3, 2, 0, C.byref(h)))
 
 
+def test_split_knob_values():
+    """Knob split selects lock-step (0, 1) or the two-stream schedule (3); 2, the retired fused
+    schedule, is out of range like any other value."""
+    from qamr import _lib
+
+    saved = _lib.tune_get("split")
+    try:
+        for v in (0, 1, 3):
+            _lib.tune_set("split", v)
+            assert _lib.tune_get("split") == v
+        for v in (2, 4):
+            with pytest.raises(ValueError):
+                _lib.tune_set("split", v)
+            assert _lib.tune_get("split") == 3  # a refused value changes nothing
+    finally:
+        _lib.tune_set("split", saved)
+    assert _lib.tune_get("split") == saved
+
+
 def test_status_mapping():
     from qamr import _lib
 

@@ -35,12 +35,16 @@ def _frames(rng, orc, B, V, sig=(0.5, 0.9)):
     return llr, synd
 
 
-@pytest.mark.parametrize("split", [1, 2, 3])
+def _high_degree_code(rng, V=300):
+    return _code(rng, [17, 33, 65, 100, 17, 5, 7], V)
+
+
+@pytest.mark.parametrize("split", [1, 3])
 def test_high_degree_checks_vs_oracle(gpu, split):
     import qamr
     rng = np.random.default_rng(17)
     V = 300
-    vid, cid = _code(rng, [17, 33, 65, 100, 17, 5, 7], V)
+    vid, cid = _high_degree_code(rng, V)
     dec = qamr.Decoder(vid, cid)
     orc = O.OracleCode(vid, cid)
     llr, synd = _frames(rng, orc, 70, V)
@@ -53,6 +57,43 @@ def test_high_degree_checks_vs_oracle(gpu, split):
     s2, i2, f2 = orc.decode_batch(llr, synd, 30)
     assert np.array_equal(s1, s2) and np.array_equal(i1, i2)
     assert_bit_exact(f1, f2)
+
+
+def _workspace_closed_form(vid, cid, ld, max_it, repack):
+    """The decode workspace's size restated from the code's counts (decoder.hip ws_layout)."""
+    A = lambda n: -(-n // 256) * 256
+    E, V, C = vid.size, int(vid.max()) + 1, int(cid.max()) + 1
+    dc, dv = np.bincount(cid), np.bincount(vid)
+    classes = np.unique(dc)
+    fb_rows = int(sum(int((dc == d).sum()) * (int(d) - 2) for d in classes if d > 16))  # runtime-degree classes
+    iter_code = len(classes) == 1 and 2 <= classes[0] <= 10 and dv.max() <= 64 and 8 * E * ld <= 1 << 30
+    base = (A(8 * E * ld) * (2 if iter_code else 1) + A(ld) + A((max(max_it, 0) + 2) * ld) + A(8 * fb_rows * ld) +
+            A(4 * ld) + 256)
+    work_set = 3 * A(8 * V * ld) + 2 * A(C * ld) + A(8 * E * ld) + A(4 * ld)
+    return base + (work_set if repack and ld % 512 == 0 else 0), fb_rows, iter_code
+
+
+def test_workspace_bytes_closed_form(gpu):
+    """Decoder.workspace_bytes equals the closed form: base part (+ second message buffer for a
+    one-launch-per-iteration code, + F scratch of the runtime-degree classes) and, with knob
+    repack on and ld % 512 == 0, the repack work set.  No kernel runs."""
+    import qamr
+    from qamr import codes
+
+    high = _high_degree_code(np.random.default_rng(17))
+    cases = [(codes.regular_code(1008), 64), (codes.regular_code(1008), 512), (high, 128)]
+    saved = qamr._lib.tune_get("repack")
+    try:
+        for repack in (1, 0):
+            qamr._lib.tune_set("repack", repack)
+            for (vid, cid), ld in cases:
+                dec = qamr.Decoder(vid, cid)
+                for max_it in (0, 30):
+                    want, fb_rows, iter_code = _workspace_closed_form(vid, cid, ld, max_it, repack)
+                    assert (fb_rows > 0) == (vid is high[0]) and iter_code == (vid is not high[0])
+                    assert dec.workspace_bytes(ld, max_it) == want, (vid.size, ld, max_it, repack)
+    finally:
+        qamr._lib.tune_set("repack", saved)
 
 
 def test_degree_255_and_all_large(gpu):

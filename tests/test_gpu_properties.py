@@ -71,9 +71,9 @@ def _dvbs2_batch(B, snr_db, seed=0):
     return vid, cid, dec, pipe, batch, lappr
 
 
-TUNINGS = [dict(split=1), dict(split=2, check_per=1), dict(check_ft=64, check_per=3, var_ft=128, var_per=1),
+TUNINGS = [dict(split=1), dict(split=3, check_per=1), dict(check_ft=64, check_per=3, var_ft=128, var_per=1),
            dict(nt=0), dict(split=1, check_ft=128, var_per=16), dict(split=3, lds_pad_kb=0, nt=0),
-           dict(split=2), dict(compact=0), dict(split=1, compact=0), dict(split=2, compact=0),
+           dict(compact=0), dict(split=1, compact=0),
            dict(side=0, compact=0), dict(min_blocks=0), dict(min_blocks=4096, split=1),
            dict(split_min_blocks=4096), dict(split_min_blocks=0, min_blocks=0),
            dict(var_pace=0), dict(var_pace=3, var_per=1, compact=0), dict(var_pace=4096),
