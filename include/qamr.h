@@ -108,7 +108,8 @@ QR_API int qr_decode_workspace_size(const qr_code *code, int32_t ld, int32_t max
  *   d_synd  [C][ld] uint8  target syndromes      (0/1)
  *   d_final [V][ld] fp64   final LAPPRs = posterior after the last variable sweep,
  *                          or a copy of d_lappr when the input already satisfies
- *                          the syndrome (decoder.pyx:400-405)
+ *                          the syndrome (decoder.pyx:400-405); the padding columns
+ *                          [B, ld) are not written
  *   d_success[B] uint8, d_iters[B] int32: the (success, iterations) pair of
  *                          _decode for every frame (decoder.pyx:433,436).
  * Per-frame early termination; results per frame are identical to decoding

@@ -417,7 +417,8 @@ __device__ __forceinline__ void check_block(const CheckArgs &a, unsigned bx, uns
 // decoder.pyx:285-298: post[v] = lappr[v] + c2v[e_0] + c2v[e_1] + ... (ascending e).
 // INIT: the first sweep with c2v == 0 (decoder.pyx:408,420-421): lappr + 0.0 for
 // frames still decoding; frames already successful at iteration 0 get a plain
-// copy of their input (decoder.pyx:404).
+// copy of their input (decoder.pyx:404).  It sweeps all ld columns but writes only frames
+// < fin_B: no sweep touches the output's padding columns [B, ld).
 // TRANSIT (the first variable sweep after a repack): the frame's LAPPRs and posterior are in
 // column f_off + lp of the new set, its messages still at its listed (old) column of the old set.
 template <bool INIT, bool NT, bool TRANSIT = false>
@@ -433,6 +434,7 @@ __device__ __forceinline__ void var_block(const VarArgs &a, unsigned bx, unsigne
     const int sub = __builtin_amdgcn_readfirstlane(threadIdx.x >> a.g.lft);
     const bool act = a.active[f] != 0;
     if (!live || (!INIT && !act)) return;
+    if (INIT && f >= a.fin_B) return;  // padding columns [B, ld): the output keeps the caller's values
     const int64_t v0 = (int64_t)bx * a.g.per * nsub + sub;
     bool big = false;
     for (int j = 0; j < a.g.per; ++j) {
@@ -584,7 +586,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))
     ClkScope clk(D == 7 && MODE == kNormal, g_clk, g_wgt);
 #endif
     if (MODE != kParityOnly) stage_glibc_tables(&tab, a.gglibc);
-    if constexpr (MODE == kNormal && kPacked<D>) {
+    // Every templated degree, packed or not: select_range has switched the launch to the new
+    // column set whatever D is, so a class that kept the listed (old) columns here would read the
+    // posteriors and flags of other frames (run_split2 takes every code of max degree <= 16).
+    if constexpr (MODE == kNormal) {
         if (a.transit) {  // kernel-uniform: the first sweep after a repack (NaN-preserving clamp)
             check_block<D, MODE, NT, false, true>(a, bx, by, per, tab, hb);
             return;

@@ -8,7 +8,8 @@ posterior and message indices (k_resident).  This test runs the repack parity te
 4-PAM 4.0 dB and 16-PAM 14.5 dB B = 4096 batches: repacks in both directions between the column
 sets, transitions, narrow sweeps; a short max_iterations; the captured decode), the schedule and
 tuning invariance test, and the frame-resident parity tests (configs[1] full batch, ragged batch
-shapes) in a child process on that library; conftest's autouse fixture fails any test after which a device check failed."""
+shapes), and the repack on small codes with an unpacked check class (degree 12 as the only class and
+as the side class: tests/test_gpu_repack_small_codes.py, every knob set) in a child process on that library; conftest's autouse fixture fails any test after which a device check failed."""
 import os
 import subprocess
 import sys
@@ -30,6 +31,8 @@ CASES = [
     "tests/test_gpu_properties.py::test_schedule_and_tuning_invariance",
     "tests/test_gpu_parity_edges.py::test_configs1_full_batch_vs_oracle",
     "tests/test_gpu_parity_edges.py::test_resident_batch_shapes_vs_oracle",
+    "tests/test_gpu_repack_small_codes.py::test_repack_small_codes_vs_oracle[reg12-clean]",
+    "tests/test_gpu_repack_small_codes.py::test_repack_small_codes_vs_oracle[side12-clean]",
 ]
 
 
@@ -40,4 +43,4 @@ def test_debug_build_device_checks(gpu):
                        env=env, capture_output=True, text=True, timeout=900)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
-    assert "12 passed" in r.stdout, tail  # the 9 cases above (the batch-shape test has 4 parameters)
+    assert "14 passed" in r.stdout, tail  # the 11 cases above (the batch-shape test has 4 parameters)
