@@ -65,7 +65,7 @@ QR_API int qr_profile_reset(void);
 QR_API int qr_profile_select(const char *names);
 /* name: "check" (one check sweep, all degree classes), "check_d<D>" (the launch
  * for check degree D), "check1" (first sweep), "var", "var_init", "status",
- * "parity", "demap", "bob", "syndrome", "count".  Synchronises pending events. */
+ * "parity", "demap", "demap_interp", "bob", "syndrome", "count".  Synchronises pending events. */
 QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launches);
 
 /* Kernel-geometry knobs (process-wide; performance only, results unchanged):
@@ -75,7 +75,12 @@ QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launche
  * iteration apart on two streams, so one half's check sweep overlaps the other
  * half's variable sweep, where a half batch fills the chip; any other value is
  * QR_EVALUE), "demap_fast" (1 = Newton-located root +
- * replayed bisection, bit-identical to 0 = the reference's brute-force search). */
+ * replayed bisection, bit-identical to 0 = the reference's brute-force search),
+ * "interp_fast" (index search of the interpolated g_inv: 1 = coarse table + segment bisection
+ * where the grid is nondecreasing, 0 = the reference's __binsearch probe for probe),
+ * "interp_seg" (log2 of the grid entries per coarse-table segment, default 4, used from 1 to 20
+ * and raised until the coarse table has at most 4096 entries; read by qr_demap_grid_create, which
+ * rebuilds a grid made under another value). */
 QR_API int qr_tune_set(const char *name, int64_t value);
 QR_API int qr_tune_get(const char *name, int64_t *value);
 
@@ -191,6 +196,38 @@ QR_API int qr_g_inv_search_host(const qr_demap *dm, int64_t n, const double *n_h
  * uniformly weighted mixture CDF (the cpdef ignores the alphabet's probabilities).  Host
  * arrays of n elements; synchronous. */
 QR_API int qr_F_Y_host(const qr_demap *dm, int64_t n, const double *y, double *F);
+
+/* -------------------------------- table-interpolated g_inv, formulation 1 */
+/* The interpolation grid of NoiseMapper.__cinit__ (noisemapper.pyx:135-144), built on demand
+ * in HBM: y_range = numpy.linspace(y_low, y_high, n_points) with the truncation rule of
+ * :135-141 and n_points of :142 (`step` is the alphabet's, pa.step), F_Y_values = F_Y(y_range)
+ * (:264-275, the function qr_F_Y_host computes).  Calling it again with the same three
+ * parameters does nothing; other parameters rebuild the tables (synchronously: no launch that
+ * reads them may be pending or captured).  QR_EVALUE unless trunkation_threshold > 0,
+ * n_intervals_per_step > 0, step > 0 and 2 <= n_points <= 2^26.  Synchronous. */
+QR_API int qr_demap_grid_create(qr_demap *dm, double trunkation_threshold, int64_t n_intervals_per_step, double step);
+/* n_points (noisemapper.pyx:142) and whether F_Y_values is nondecreasing (checked in one pass
+ * when the grid is built; the shortcut index search is used only then).  QR_EVALUE before
+ * qr_demap_grid_create. */
+QR_API int qr_demap_grid_info(const qr_demap *dm, int32_t *n_points, int32_t *nondecreasing);
+/* NoiseMapper.y_range / F_Y_values (noisemapper.pyx:255-261): host arrays of n_points doubles
+ * (either may be NULL). */
+QR_API int qr_demap_grid_host(const qr_demap *dm, double *y_range, double *F_Y_values);
+/* NoiseMapper.g_inv (noisemapper.pyx:295-307) over arrays, i.e. NoiseMapper.demap_noise
+ * (:391-403): y_hat[k] = __interp(F_Y_values, y_range, target(n_hat[k], i[k])) with
+ * __binsearch / __interp of :27-63.  Bit-identical to the reference; i[k] outside [0, M) gives
+ * NaN (out-of-bounds reads in the reference).  Host arrays of n elements; synchronous. */
+QR_API int qr_g_inv_host(const qr_demap *dm, int64_t n, const double *n_hat, const int64_t *i, double *y_hat);
+/* NoiseMapper.demap_lappr_simplified_array ("Formulation 1", noisemapper.pyx:563-620) for one
+ * array from host memory: lappr[S*bps], any bit_per_symbol.  Out-of-range symbol indices
+ * yield NaN LAPPRs. */
+QR_API int qr_demap_simplified_host(const qr_demap *dm, int64_t S, const double *n, const int64_t *j, double *lappr);
+/* Batched NoiseMapper.demap_lappr_simplified_array (noisemapper.pyx:563-620) fused with the LLR
+ * scaling (reconciliation.pyx:143-145); arguments, layouts and the NaN convention of
+ * qr_demap_batch_device.  QR_EVALUE if the grid has not been created, QR_EUNSUPPORTED for
+ * bit_per_symbol > 6.  The padding columns [B, ld) are not written. */
+QR_API int qr_demap_simplified_batch_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, const double *d_n,
+                                            const int64_t *d_j, double alpha, double *d_lappr, void *stream);
 
 /* ---------------------------------------------- softening pipeline (Bob) */
 /* NoiseMapper.hard_decide_index + map_noise (noisemapper.pyx:349-388) and

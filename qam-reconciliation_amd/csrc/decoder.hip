@@ -76,6 +76,7 @@ enum DebugSite {
     kDbgCompact = 7,       // k_compact: list index outside the range
     kDbgResPost = 8,       // k_resident: posterior index outside [0, V)
     kDbgResMsg = 9,        // k_resident: LDS message index outside [0, C D)
+    // 10, 11: the interpolation grid's index checks (demap.hip, GridDebugSite)
 };
 
 // Check-node arithmetic: the reference's box-plus bit for bit -- glibc exp/log restated
@@ -2282,6 +2283,11 @@ QR_API int qr_debug_asserts(int64_t *out) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(qr::g_dbg), sizeof(h)) != hipSuccess) return QR_EDEVICE;
     const unsigned long long z[4] = {0, 0, 0, 0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(qr::g_dbg), z, sizeof(z)) != hipSuccess) return QR_EDEVICE;
+    unsigned long long d[4] = {0, 0, 0, 0};   // the interpolation grid's checks (demap.hip)
+    if (int rc = qr::debug_asserts_demap(d)) return rc;
+    if (h[0] == 0)
+        for (int i = 1; i < 4; ++i) h[i] = d[i];
+    h[0] += d[0];
     for (int i = 0; i < 4; ++i) out[i] = (int64_t)h[i];
     return QR_OK;
 }
@@ -2314,6 +2320,7 @@ static std::atomic<int> *tune_knob(const char *name) {
         {"lds_pad_kb", &g_tune.lds_pad_kb}, {"compact", &g_tune.compact},
         {"side", &g_tune.side},             {"demap_fast", &g_demap_fast},
         {"demap_hyp", &g_demap_hyp},        {"min_blocks", &g_tune.min_blocks},
+        {"interp_fast", &g_interp_fast},    {"interp_seg", &g_interp_seg},
         {"split_min_blocks", &g_tune.split_min_blocks},
         {"var_pace", &g_tune.var_pace},     {"check_tail", &g_tune.check_tail}, {"var_boost", &g_tune.var_boost},
         {"fused_iter", &g_tune.fused_iter}, {"iter_streams", &g_tune.iter_streams},

@@ -11,6 +11,10 @@
 // i order.  This is fp64-VALU bound (bytes are negligible); lanes of a wave
 // hold 64 consecutive frames of the same symbol position so the LAPPR stores
 // land directly, coalesced, in the decoder's frame-innermost input layout.
+//
+// The reference's second demapper ("Formulation 1", noisemapper.pyx:563-620) inverts F_Y by
+// interpolation in the tabulated grid instead (g_inv, :295-307): k_demap_interp_wave below, on
+// the same tiles, bound by its dependent index-search loads rather than by fp64 VALU.
 #include <atomic>
 #include <vector>
 
@@ -374,6 +378,257 @@ __global__ void __launch_bounds__(256) k_public_F_Y(const DemapTables *__restric
     if (k < n) F[k] = public_F_Y(*tab, y[k]);
 }
 
+// ---------------------------------------------------------------------------
+// Table-interpolated g_inv (noisemapper.pyx:295-307) and the formulation-1 demapper built on it
+// (demap_lappr_simplified, noisemapper.pyx:563-601).
+//
+// The grid of noisemapper.pyx:135-144 lives in HBM as n {F[r], y[r]} pairs (qr_demap_grid_create):
+// y = numpy's linspace(y_low, y_high, n), F = the cpdef F_Y of it (public_F_Y, the uniform
+// mixture).  g_inv(n_hat, i) = __interp(F, y, target) (noisemapper.pyx:47-63): the index r of
+// __binsearch (:27-44), then a linear interpolation between pairs r and r + 1, which are 32
+// contiguous bytes.
+//
+// Index search, two bodies:
+//  (a) grid_binsearch: the reference's recursion, iterated -- the same probes in the same
+//      order, so it returns the reference's index on ANY table;
+//  (b) grid_interp_fast: "the last r with F[r] <= val (0 when val < F[0])" by bisection of a
+//      coarse table (every 16th F by default, in LDS for the wave kernel) and then of the one
+//      16-entry segment in HBM (at most 4 steps).  On a nondecreasing table (a) returns exactly
+//      that index:
+//      a probe sequence of (a) keeps the invariant F[base] <= val (or base = 0) and
+//      val < F[base + size] (or base + size = n), it only ever discards entries on the strength
+//      of one comparison val < F[k] (everything from k on is > val) or val >= F[k] (everything up
+//      to k is <= val), and it stops at an index r with F[r] <= val < F[r + 1], or at the last
+//      entry of its range when val exceeds it -- with ties, always the last of the tied run,
+//      because val >= F[index + 1] sends it right.  F is a rounded sum of erf terms, so nothing
+//      guarantees that it is nondecreasing: qr_demap_grid_create checks it in one pass and (b) is
+//      used only when the check passed (and val is not NaN).
+//      Knob interp_fast = 0 forces (a).
+constexpr int kGridMaxCoarse = 4096;  // coarse entries the wave kernel stages in LDS (32 KiB)
+std::atomic<int> g_interp_fast{1};
+// log2 of the entries per coarse-table segment, read when a grid is created (knob interp_seg,
+// clamped to 1..20); a grid too long for kGridMaxCoarse segments of that size takes the next size
+// that fits.  Every divergent probe of the grid in HBM costs the CU's vector-memory pipe a cache
+// line per lane, a probe of the LDS table far less, so smaller segments are faster until the LDS
+// table cuts the occupancy: 16-PAM 13 dB, B = 4096 (29 354 points): 14.6 / 13.2 / 11.8 / 11.7 ms
+// at 64 / 32 / 16 / 8 entries, 4-PAM 3 dB (14 009 points) 7.3 / 6.8 / 6.3 / 5.8 ms
+// (profiles/interp/README.md); 16 keeps the table under 32 KiB up to 65 536 points.
+std::atomic<int> g_interp_seg{4};
+
+struct GridView {
+    const double2 *pairs;   // [n] {F, y}
+    const double *coarse;   // [nc] F[c << seg_shift]
+    int32_t n, nc, seg_shift;
+    double F_last, y_last;  // pairs[n - 1]
+};
+
+#if QR_DEBUG_ASSERT
+__device__ unsigned long long g_dbg_demap[4];  // {failed checks, first site, first a, first b}
+__device__ __noinline__ void dcheck_fail_demap(int site, long long a, long long b) {
+    if (atomicAdd(&g_dbg_demap[0], 1ull) == 0ull) {
+        g_dbg_demap[1] = (unsigned long long)site;
+        g_dbg_demap[2] = (unsigned long long)a;
+        g_dbg_demap[3] = (unsigned long long)b;
+        printf("qamr debug check %d failed: a=%lld b=%lld (block %u thread %u)\n", site, a, b, blockIdx.x, threadIdx.x);
+    }
+}
+#define QR_DCHECK(ok, site, a, b)                                         \
+    do {                                                                  \
+        if (!(ok)) dcheck_fail_demap((site), (long long)(a), (long long)(b)); \
+    } while (0)
+#else
+#define QR_DCHECK(ok, site, a, b) ((void)0)
+#endif
+enum GridDebugSite {
+    kDbgGridIndex = 10,    // grid index r outside [0, n), or r + 1 read with r + 1 >= n
+    kDbgGridCoarse = 11,   // coarse-table index outside [0, nc)
+};
+
+// noisemapper.pyx:27-44 (__binsearch) over the F of the pairs, iterated: slice = [base, base + size).
+__device__ __forceinline__ int grid_binsearch(const GridView &g, double val) {
+    int base = 0, size = g.n;
+    for (;;) {
+        QR_DCHECK(base >= 0 && size >= 1 && base + size <= g.n, kDbgGridIndex, base, size);
+        if (size == 1) return base;
+        if (val < g.pairs[base].x) return base;
+        if (val > g.pairs[base + size - 1].x) return base + size - 1;
+        const int index = size / 2 - 1;
+        if (val < g.pairs[base + index].x) { size = index; continue; }
+        if (val >= g.pairs[base + index + 1].x) { base += index + 1; size -= index + 1; continue; }
+        return base + index;
+    }
+}
+
+// Body (b) with the interpolation: the last r with F[r] <= val (0 when val < F[0]) and
+// __interp's result at it; val is not NaN and val < F[n - 1].  coarse: the coarse table (LDS or
+// HBM).  The segment's probes load whole pairs, and the last two probes of a bisection are r and
+// r + 1 themselves, so the interpolation operands are usually in registers already; only when r
+// is the first or r + 1 is past the last entry probed in the segment is a pair loaded again.
+__device__ __forceinline__ double grid_interp_fast(const GridView &g, const double *coarse, double val) {
+    int a = 0, b = 1;        // the pairs r = a and r + 1 = b ...
+    double2 pa, pb;          // ... once loaded
+    bool have_a = false, have_b = false;
+    if (!(val < coarse[0])) {
+        int lo = 0, hi = g.nc;   // coarse[lo] <= val, and hi == nc or coarse[hi] > val
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            QR_DCHECK(mid >= 0 && mid < g.nc, kDbgGridCoarse, mid, g.nc);
+            if (coarse[mid] <= val) lo = mid; else hi = mid;
+        }
+        a = lo << g.seg_shift;   // F[a] <= val; at most seg_shift steps inside the segment
+        b = a + (1 << g.seg_shift) < g.n ? a + (1 << g.seg_shift) : g.n;
+        while (b - a > 1) {
+            const int mid = (a + b) >> 1;
+            QR_DCHECK(mid >= 0 && mid < g.n, kDbgGridIndex, mid, g.n);
+            const double2 p = g.pairs[mid];
+            if (p.x <= val) { a = mid; pa = p; have_a = true; }
+            else            { b = mid; pb = p; have_b = true; }
+        }
+    }
+    QR_DCHECK(a >= 0 && a < g.n && b == a + 1, kDbgGridIndex, a, b);
+    if (a == g.n - 1) return g.y_last;               // noisemapper.pyx:55-56
+    if (!have_a) pa = g.pairs[a];
+    QR_DCHECK(a + 1 < g.n, kDbgGridIndex, a + 1, g.n);
+    if (!have_b) pb = g.pairs[a + 1];
+    if (pb.x == pa.x) return pa.y;                   // :58-59
+    return pa.y + (pb.y - pa.y) * (val - pa.x) / (pb.x - pa.x);   // :61-63
+}
+
+// noisemapper.pyx:295-307 (g_inv) with __interp (:47-63): left to right, unfused.
+template <bool FAST>
+__device__ __forceinline__ double grid_g_inv(const DemapTables &t, const GridView &g, const double *coarse,
+                                             double n_hat, int i) {
+    const double val = search_target(t, n_hat, i);   // the same expression as g_inv_search's (:297-307)
+    if (val >= g.F_last) return g.y_last;            // :50-51
+    if (FAST && val == val) return grid_interp_fast(g, coarse, val);
+    const int r = grid_binsearch(g, val);
+    QR_DCHECK(r >= 0 && r < g.n, kDbgGridIndex, r, g.n);
+    if (r == g.n - 1) return g.y_last;               // :55-56
+    QR_DCHECK(r + 1 < g.n, kDbgGridIndex, r + 1, g.n);
+    const double2 p0 = g.pairs[r], p1 = g.pairs[r + 1];
+    if (p1.x == p0.x) return p0.y;                   // :58-59
+    return p0.y + (p1.y - p0.y) * (val - p0.x) / (p1.x - p0.x);   // :61-63
+}
+
+// Formulation 1 on 64-frame tiles, indexed as k_demap_wave: lane = frame, one wave per 64-frame
+// tile of one symbol row, grid-stride.  Per hypothesis i (ascending, noisemapper.pyx:587-596):
+// y_i = g_inv(n, i), one exp(-((y_i - a_j)**2) / 2 sigma^2) (the reference evaluates the same
+// expression once per bit k; Cython's pow(x, 2.0) is compiled to x * x), added to N[k] or D[k]
+// by the Gray test of i -- wave-uniform, so the sums stay in registers.  glibc's exp and log
+// restated (subnormal and zero sums, log(0) = -inf, are reached at high SNR).
+template <int BPS, bool FAST>
+__global__ void __launch_bounds__(256) k_demap_interp_wave(const DemapTables *__restrict__ tab, const GridView g,
+                                                           int B, int ld, int64_t S, const double *__restrict__ n,
+                                                           const int64_t *__restrict__ j, double alpha,
+                                                           double *__restrict__ lappr) {
+    constexpr int M = 1 << BPS;
+    __shared__ GlibcExpLog gt;
+    extern __shared__ double coarse[];   // FAST: g.nc entries
+    stage_glibc_exp_log(&gt, &kGlibcConst);
+    if (FAST) {
+        for (int c = threadIdx.x; c < g.nc; c += blockDim.x) coarse[c] = g.coarse[c];
+        __syncthreads();
+    }
+    const DemapTables &t = *tab;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t tiles = ld / 64;
+    const int64_t items = S * tiles;
+    for (int64_t it = (int64_t)blockIdx.x * 4 + w; it < items; it += (int64_t)gridDim.x * 4) {   // wave-uniform
+        const int64_t s = it / tiles;
+        const int f = (int)(it - s * tiles) * 64 + lane;
+        const bool valid = f < B;
+        const double nv = valid ? n[s * ld + f] : 0.5;   // padding lanes: a harmless target
+        const int64_t jv = valid ? j[s * ld + f] : 0;
+        const bool jok = jv >= 0 && jv < M;
+        const double aj = t.a[jok ? (int)jv : 0];
+        double N[BPS], D[BPS];
+#pragma unroll
+        for (int k = 0; k < BPS; ++k) { N[k] = 0; D[k] = 0; }
+#pragma unroll 1
+        for (int i = 0; i < M; ++i) {
+            const double y = grid_g_inv<FAST>(t, g, coarse, nv, i);
+            const double d = y - aj;
+            const double e = g_exp_full(-(d * d) / t.two_s2, gt);
+            int mi = i;
+#pragma unroll
+            for (int k = 0; k < BPS; ++k) {   // noisemapper.pyx:590-596: Gray bit k of i
+                if ((mi * (mi + 1)) & 3) D[k] += e;
+                else                     N[k] += e;
+                mi >>= 1;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < BPS; ++k) {
+            const double out = (g_log_full(N[k], gt) - g_log_full(D[k], gt)) * alpha;   // :598-599, x alpha
+            if (valid) lappr[(s * BPS + k) * ld + f] = jok ? out : __builtin_nan("");
+        }
+    }
+}
+
+// One lane per element, for the host entry points (any bps): formulation 1 of symbol s into
+// lappr[s * bps + k] (noisemapper.pyx:605-620), the coarse table read from HBM.
+template <bool FAST>
+__global__ void __launch_bounds__(256) k_demap_interp_lane(const DemapTables *__restrict__ tab, const GridView g,
+                                                           int64_t S, const double *__restrict__ n,
+                                                           const int64_t *__restrict__ j,
+                                                           double *__restrict__ lappr) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const DemapTables &t = *tab;
+    const int64_t jv = j[s];
+    if (jv < 0 || jv >= t.M) {
+        for (int k = 0; k < t.bps; ++k) lappr[s * t.bps + k] = __builtin_nan("");
+        return;
+    }
+    const double nv = n[s], aj = t.a[jv];
+    double N[kMaxBps], D[kMaxBps];
+#pragma unroll
+    for (int k = 0; k < kMaxBps; ++k) { N[k] = 0; D[k] = 0; }
+    for (int i = 0; i < t.M; ++i) {
+        const double y = grid_g_inv<FAST>(t, g, g.coarse, nv, i);
+        const double d = y - aj;
+        const double e = g_exp_full(-(d * d) / t.two_s2, kGlibcConst);
+        int mi = i;
+#pragma unroll
+        for (int k = 0; k < kMaxBps; ++k) {
+            if (k < t.bps) {
+                if ((mi * (mi + 1)) & 3) D[k] += e;
+                else                     N[k] += e;
+                mi >>= 1;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxBps; ++k)
+        if (k < t.bps) lappr[s * t.bps + k] = g_log_full(N[k], kGlibcConst) - g_log_full(D[k], kGlibcConst);
+}
+
+// noisemapper.pyx:391-403 (demap_noise): y_hat[k] = g_inv(n_hat[k], i[k]); an out-of-range i
+// gives NaN (the reference indexes sign_config / F_Y_thresholds out of bounds).
+template <bool FAST>
+__global__ void __launch_bounds__(256) k_g_inv_interp(const DemapTables *__restrict__ tab, const GridView g, int64_t n,
+                                                      const double *__restrict__ n_hat,
+                                                      const int64_t *__restrict__ idx, double *__restrict__ y_hat) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const DemapTables &t = *tab;
+    const int64_t i = idx[k];
+    y_hat[k] = (i < 0 || i >= t.M) ? __builtin_nan("") : grid_g_inv<FAST>(t, g, g.coarse, n_hat[k], (int)i);
+}
+
+// The grid itself (noisemapper.pyx:143-144): y[i] as numpy's linspace computes it,
+// fl(fl(i * step) + y_low) with the last point set to y_high, and F = the cpdef F_Y of it.
+__global__ void __launch_bounds__(256) k_grid_build(const DemapTables *__restrict__ tab, int32_t n, double y_low,
+                                                    double y_high, double step, double2 *__restrict__ pairs) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double y = (i == n - 1) ? y_high : (double)i * step + y_low;
+    double2 p;
+    p.x = public_F_Y(*tab, y);
+    p.y = y;
+    pairs[i] = p;
+}
+
 // matrix.pyx:55-60, frame-innermost; one lane = (check, frame).
 __global__ void __launch_bounds__(256) k_syndrome(int64_t C, int ld, int B, const int32_t *__restrict__ chk_ptr,
                                                   const int32_t *__restrict__ chk_var,
@@ -458,6 +713,58 @@ int demap_batch_device(const qr_demap *dm, int B, int ld, int64_t S, const doubl
     return QR_OK;
 }
 
+static GridView grid_view(const qr_demap *dm) {
+    const DemapGrid &gr = dm->grid;
+    return GridView{gr.d_pairs, gr.d_coarse, gr.n, gr.nc, gr.seg_shift, gr.h_pairs.back().x, gr.h_pairs.back().y};
+}
+
+// body (b) of the index search: the table certified nondecreasing and the knob on
+static bool grid_fast(const qr_demap *dm) { return dm->grid.nondecreasing && g_interp_fast.load() != 0; }
+
+template <bool FAST>
+static bool launch_demap_interp_wave(int bps, unsigned grid, size_t lds, hipStream_t st, const qr_demap *dm,
+                                     const GridView &g, int B, int ld, int64_t S, const double *n, const int64_t *j,
+                                     double alpha, double *lappr) {
+    switch (bps) {
+#define QR_DEMAP_INTERP(b) \
+        case b: k_demap_interp_wave<b, FAST><<<grid, 256, lds, st>>>(dm->d_tables, g, B, ld, S, n, j, alpha, lappr); return true;
+        QR_DEMAP_INTERP(1) QR_DEMAP_INTERP(2) QR_DEMAP_INTERP(3) QR_DEMAP_INTERP(4) QR_DEMAP_INTERP(5) QR_DEMAP_INTERP(6)
+#undef QR_DEMAP_INTERP
+        default: return false;
+    }
+}
+
+int demap_simplified_batch_device(const qr_demap *dm, int B, int ld, int64_t S, const double *n, const int64_t *j,
+                                  double alpha, double *lappr, hipStream_t s) {
+    int rc = check_shape(B, ld, S);
+    if (rc) return rc;
+    if (dm->grid.n <= 0) return set_error(QR_EVALUE, "the interpolation grid has not been created (qr_demap_grid_create)");
+    if (dm->h.bps > kDemapWaveMaxBps)
+        return set_error(QR_EUNSUPPORTED, "the batched demapper serves bit_per_symbol <= %d (got %d)", kDemapWaveMaxBps,
+                         dm->h.bps);
+    DeviceGuard g(dm->device);
+    ProfScope ps("demap_interp", s);
+    const GridView gv = grid_view(dm);
+    const int64_t items = S * (ld / kWave);
+    const unsigned grid = demap_wave_grid(dm->device, (items + 3) / 4);
+    if (grid_fast(dm))   // nc <= kGridMaxCoarse by construction
+        launch_demap_interp_wave<true>(dm->h.bps, grid, (size_t)gv.nc * sizeof(double), s, dm, gv, B, ld, S, n, j, alpha,
+                                       lappr);
+    else
+        launch_demap_interp_wave<false>(dm->h.bps, grid, 0, s, dm, gv, B, ld, S, n, j, alpha, lappr);
+    QR_LAUNCH_CHECK();
+    return QR_OK;
+}
+
+#if QR_DEBUG_ASSERT
+int debug_asserts_demap(unsigned long long h[4]) {
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dbg_demap), 4 * sizeof(unsigned long long)) != hipSuccess) return QR_EDEVICE;
+    const unsigned long long z[4] = {0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_demap), z, sizeof(z)) != hipSuccess) return QR_EDEVICE;
+    return QR_OK;
+}
+#endif
+
 }  // namespace qr
 
 // ===================================================================== C-ABI
@@ -539,9 +846,152 @@ int qr_demap_destroy(qr_demap *dm) {
         (void)hipFree(dm->d_mtab);
         (void)hipFree(dm->d_quant);
         (void)hipFree(dm->d_ftab);
+        (void)hipFree(dm->grid.d_pairs);
+        (void)hipFree(dm->grid.d_coarse);
     }
     delete dm;
     return QR_OK;
+}
+
+int qr_demap_grid_create(qr_demap *dm, double trunkation_threshold, int64_t n_intervals_per_step, double step) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (!(trunkation_threshold > 0) || n_intervals_per_step <= 0 || !(step > 0))
+        return set_error(QR_EVALUE, "grid: need trunkation_threshold > 0, n_intervals_per_step > 0, step > 0");
+    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    DemapGrid &gr = dm->grid;
+    if (gr.n > 0 && gr.trunc == trunkation_threshold && gr.nips == n_intervals_per_step && gr.step == step &&
+        gr.seg_req == g_interp_seg.load())
+        return QR_OK;
+    const DemapTables &t = dm->h;
+    const double sigma = sqrt(t.two_s2 / 2);   // noisemapper.pyx:132 (two_s2 / 2 = noise_var, exactly)
+    double y_low, y_high;
+    if (trunkation_threshold > 1.) {           // :135-137
+        y_low = t.a[0] * 10;
+        y_high = t.a[t.M - 1] * 10;
+    } else {                                   // :138-141
+        const double tmp = sqrt(-2. * log(trunkation_threshold)) * sigma;
+        y_high = t.a[t.M - 1] + tmp;
+        y_low = t.a[0] - tmp;
+    }
+    const double np = ceil((y_high - y_low) * (double)n_intervals_per_step / step) + 1;   // :142
+    if (!(np >= 2 && np <= (double)(1 << 26)))
+        return set_error(QR_EVALUE, "grid: %g points (need 2 .. 2^26)", np);
+    const int32_t n = (int32_t)np;
+    int32_t seg_shift = g_interp_seg.load();
+    seg_shift = seg_shift < 1 ? 1 : seg_shift > 20 ? 20 : seg_shift;
+    while (((n - 1) >> seg_shift) + 1 > kGridMaxCoarse) ++seg_shift;
+    const int32_t nc = ((n - 1) >> seg_shift) + 1;
+    const double lin_step = (y_high - y_low) / (double)(n - 1);   // numpy.linspace: delta / div
+    DeviceGuard g(dm->device);
+    double2 *d_pairs = nullptr;
+    double *d_coarse = nullptr;
+    std::vector<double2> h((size_t)n);
+    std::vector<double> coarse((size_t)nc);
+    hipError_t e = hipMalloc((void **)&d_pairs, (size_t)n * sizeof(double2));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_coarse, (size_t)nc * sizeof(double));
+    if (e == hipSuccess) {
+        k_grid_build<<<(unsigned)((n + 255) / 256), 256>>>(dm->d_tables, n, y_low, y_high, lin_step, d_pairs);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(h.data(), d_pairs, (size_t)n * sizeof(double2), hipMemcpyDeviceToHost);
+    int nondecreasing = 1;
+    if (e == hipSuccess) {
+        for (int32_t r = 0; r + 1 < n; ++r)
+            if (!(h[r + 1].x >= h[r].x)) nondecreasing = 0;
+        for (int32_t c = 0; c < nc; ++c) coarse[c] = h[(size_t)c << seg_shift].x;
+        e = hipMemcpy(d_coarse, coarse.data(), (size_t)nc * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(d_pairs);
+        (void)hipFree(d_coarse);
+        return hip_fail(e, "qr_demap_grid_create", __FILE__, __LINE__);
+    }
+    (void)hipFree(gr.d_pairs);   // a rebuild with other parameters replaces the tables
+    (void)hipFree(gr.d_coarse);
+    gr.d_pairs = d_pairs;
+    gr.d_coarse = d_coarse;
+    gr.h_pairs.swap(h);
+    gr.n = n;
+    gr.nc = nc;
+    gr.seg_shift = seg_shift;
+    gr.seg_req = g_interp_seg.load();
+    gr.nondecreasing = nondecreasing;
+    gr.trunc = trunkation_threshold;
+    gr.nips = n_intervals_per_step;
+    gr.step = step;
+    return QR_OK;
+}
+
+int qr_demap_grid_info(const qr_demap *dm, int32_t *n_points, int32_t *nondecreasing) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (dm->grid.n <= 0) return set_error(QR_EVALUE, "the interpolation grid has not been created (qr_demap_grid_create)");
+    if (n_points) *n_points = dm->grid.n;
+    if (nondecreasing) *nondecreasing = dm->grid.nondecreasing;
+    return QR_OK;
+}
+
+int qr_demap_grid_host(const qr_demap *dm, double *y, double *F) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (dm->grid.n <= 0) return set_error(QR_EVALUE, "the interpolation grid has not been created (qr_demap_grid_create)");
+    for (int32_t r = 0; r < dm->grid.n; ++r) {
+        if (F) F[r] = dm->grid.h_pairs[r].x;
+        if (y) y[r] = dm->grid.h_pairs[r].y;
+    }
+    return QR_OK;
+}
+
+int qr_g_inv_host(const qr_demap *dm, int64_t n, const double *n_hat, const int64_t *i, double *y_hat) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (dm->grid.n <= 0) return set_error(QR_EVALUE, "the interpolation grid has not been created (qr_demap_grid_create)");
+    if (n < 0) return set_error(QR_EVALUE, "negative size");
+    if (n == 0) return QR_OK;
+    if (!n_hat || !i || !y_hat) return set_error(QR_EVALUE, "null pointer argument");
+    DeviceGuard g(dm->device);
+    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    double *d_n, *d_y;
+    int64_t *d_i;
+    if (int rc = dm->scratch.take(&d_n, (size_t)n, &d_i, (size_t)n, &d_y, (size_t)n)) return rc;
+    QR_HIP(hipMemcpy(d_n, n_hat, (size_t)n * 8, hipMemcpyHostToDevice));
+    QR_HIP(hipMemcpy(d_i, i, (size_t)n * 8, hipMemcpyHostToDevice));
+    const GridView gv = grid_view(dm);
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (grid_fast(dm)) k_g_inv_interp<true><<<grid, 256>>>(dm->d_tables, gv, n, d_n, d_i, d_y);
+    else k_g_inv_interp<false><<<grid, 256>>>(dm->d_tables, gv, n, d_n, d_i, d_y);
+    QR_LAUNCH_CHECK();
+    QR_HIP(hipMemcpy(y_hat, d_y, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return QR_OK;
+}
+
+int qr_demap_simplified_host(const qr_demap *dm, int64_t S, const double *n, const int64_t *j, double *lappr) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (dm->grid.n <= 0) return set_error(QR_EVALUE, "the interpolation grid has not been created (qr_demap_grid_create)");
+    if (S < 0) return set_error(QR_EVALUE, "negative size");
+    if (S == 0) return QR_OK;
+    if (!n || !j || !lappr) return set_error(QR_EVALUE, "null pointer argument");
+    DeviceGuard g(dm->device);
+    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    const int bps = dm->h.bps;
+    double *d_n, *d_l;
+    int64_t *d_j;
+    if (int rc = dm->scratch.take(&d_n, (size_t)S, &d_j, (size_t)S, &d_l, (size_t)S * bps)) return rc;
+    QR_HIP(hipMemcpy(d_n, n, (size_t)S * 8, hipMemcpyHostToDevice));
+    QR_HIP(hipMemcpy(d_j, j, (size_t)S * 8, hipMemcpyHostToDevice));
+    const GridView gv = grid_view(dm);
+    const unsigned grid = (unsigned)((S + 255) / 256);
+    {
+        ProfScope ps("demap_interp", nullptr);
+        if (grid_fast(dm)) k_demap_interp_lane<true><<<grid, 256>>>(dm->d_tables, gv, S, d_n, d_j, d_l);
+        else k_demap_interp_lane<false><<<grid, 256>>>(dm->d_tables, gv, S, d_n, d_j, d_l);
+        QR_LAUNCH_CHECK();
+    }
+    QR_HIP(hipMemcpy(lappr, d_l, (size_t)S * bps * 8, hipMemcpyDeviceToHost));
+    return QR_OK;
+}
+
+int qr_demap_simplified_batch_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, const double *d_n,
+                                     const int64_t *d_j, double alpha, double *d_lappr, void *stream) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    return demap_simplified_batch_device(dm, B, ld, S, d_n, d_j, alpha, d_lappr, (hipStream_t)stream);
 }
 
 int qr_demap_tables(const qr_demap *dm, double *Fthr, double *dF) {

@@ -92,6 +92,19 @@ int launch_transpose_to_fi_i64(int B, int ld, int64_t n, const int64_t *src, int
 
 extern std::atomic<int> g_demap_fast;  // demap.hip (tuning knob "demap_fast")
 extern std::atomic<int> g_demap_hyp;   // demap.hip (tuning knob "demap_hyp")
+extern std::atomic<int> g_interp_fast; // demap.hip (tuning knob "interp_fast")
+extern std::atomic<int> g_interp_seg;  // demap.hip (tuning knob "interp_seg")
+
+// Debug build (libqamr_debug.so, QR_DEBUG_ASSERT=1): device-side index checks.  decoder.hip and
+// demap.hip each count their own failed checks; qr_debug_asserts (decoder.hip) reports both.
+#ifndef QR_DEBUG_ASSERT
+#define QR_DEBUG_ASSERT 0
+#endif
+#if QR_DEBUG_ASSERT
+// demap.hip: h = {failed checks, first site, first a, first b} of the interpolation grid's index
+// checks; reads and clears them.
+int debug_asserts_demap(unsigned long long h[4]);
+#endif
 
 struct DeviceGuard {
     explicit DeviceGuard(int dev) {
@@ -178,8 +191,24 @@ struct qr_code {
     mutable hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
+// Interpolation grid of NoiseMapper.g_inv (noisemapper.pyx:135-144), built on demand by
+// qr_demap_grid_create: the tabulated uniform-mixture CDF and its abscissae, interleaved.
+struct DemapGrid {
+    int32_t n = 0;                 // n_points (0 = not created)
+    int32_t nc = 0;                // entries of the coarse table, ceil(n / 2^seg_shift)
+    int32_t seg_shift = 0;         // log2 of the entries per coarse-table segment
+    int32_t seg_req = 0;           // the knob value it was built under
+    int nondecreasing = 0;         // F[r + 1] >= F[r] for every r (one pass at creation)
+    double trunc = 0, step = 0;    // the parameters it was built from
+    int64_t nips = 0;
+    double2 *d_pairs = nullptr;    // [n] {F[r], y[r]}
+    double *d_coarse = nullptr;    // [nc] F[c << seg_shift]
+    std::vector<double2> h_pairs;  // host copy (qr_demap_grid_host)
+};
+
 struct qr_demap {
     int device = 0;
+    DemapGrid grid;                         // guarded by scratch.mu while it is (re)built
     qr::DemapTables h;                      // host copy
     qr::DemapTables *d_tables = nullptr;    // device copy
     qr::MathTables *d_mtab = nullptr;       // exp table for the Newton root search

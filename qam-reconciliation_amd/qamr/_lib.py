@@ -54,6 +54,12 @@ SIGNATURES = {
     "qr_demap_host": [vp, i64, vp, vp, vp],
     "qr_g_inv_search_host": [vp, i64, vp, vp, f64, vp],
     "qr_F_Y_host": [vp, i64, vp, vp],
+    "qr_demap_grid_create": [vp, f64, i64, f64],
+    "qr_demap_grid_info": [vp, P(i32), P(i32)],
+    "qr_demap_grid_host": [vp, vp, vp],
+    "qr_g_inv_host": [vp, i64, vp, vp, vp],
+    "qr_demap_simplified_host": [vp, i64, vp, vp, vp],
+    "qr_demap_simplified_batch_device": [vp, i32, i32, i64, vp, vp, f64, vp, vp],
     "qr_bob_map_device": [vp, i32, i32, i64, vp, vp, vp, vp, vp],
     "qr_map_noise_device": [vp, i32, i32, i64, vp, vp, vp, vp],
     "qr_syndrome_device": [vp, i32, i32, vp, vp, vp],

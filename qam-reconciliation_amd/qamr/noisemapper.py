@@ -12,6 +12,11 @@ of noisemapper.pyx:166-235.
 Batched device methods (torch tensors in HBM, frame-innermost layout):
 ``demap_device`` (fused with the LLR scaling alpha of reconciliation.pyx:144-145,
 writing the decoder's input layout directly) and ``bob_map_device``.
+
+The table-interpolated surface (``g_inv``, ``demap_noise``, noisemapper.pyx:295-307, 391-403)
+and the formulation-1 demapper on it (``demap_lappr_simplified`` / ``_array``, :563-620,
+batched: ``demap_simplified_device``) run on the interpolation grid in HBM, which libqamr
+builds on their first use (``qr_demap_grid_create``), never in ``__init__``.
 """
 from __future__ import annotations
 
@@ -254,6 +259,73 @@ class NoiseMapper:
         """noisemapper.pyx:450-540 for one symbol."""
         return self.demap_lappr_array(np.array([float(n)]), np.array([int(j)], np.int64))
 
+    # ------------------------- table-interpolated g_inv and formulation 1 (GPU)
+    def _device_grid(self):
+        """The interpolation grid in HBM (noisemapper.pyx:135-144), created on first use of the
+        interpolated methods (never in __init__); repeated calls cost one no-op C call."""
+        check(_lib.load().qr_demap_grid_create(self._h, self._trunc, self._nips, float(self._step)), "grid")
+
+    def grid_info(self):
+        """(n_points, nondecreasing) of the device grid: noisemapper.pyx:142, and whether
+        F_Y_values never decreases (the shortcut index search runs only then)."""
+        self._device_grid()
+        n, nd = C.c_int32(0), C.c_int32(0)
+        check(_lib.load().qr_demap_grid_info(self._h, C.byref(n), C.byref(nd)), "grid_info")
+        return int(n.value), bool(nd.value)
+
+    def grid_tables(self):
+        """(y_range, F_Y_values) as the device built them (equal to the properties' bits)."""
+        n, _ = self.grid_info()
+        y, F = np.empty(n, np.float64), np.empty(n, np.float64)
+        check(_lib.load().qr_demap_grid_host(self._h, ptr(y), ptr(F)), "grid_host")
+        return y, F
+
+    def g_inv(self, n_hat, i):
+        """noisemapper.pyx:295-307: y_hat by interpolation in the tabulated F_Y."""
+        return float(self.demap_noise(np.array([float(n_hat)]), np.array([int(i)], np.int64))[0])
+
+    def demap_noise(self, n_hat, symb):
+        """noisemapper.pyx:391-403: g_inv over arrays."""
+        n_hat = np.asarray(n_hat)
+        symb = np.asarray(symb)
+        if n_hat.dtype != np.float64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{n_hat.dtype}'")
+        if symb.dtype != np.int64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'long' but got '{symb.dtype}'")
+        if n_hat.size != symb.size:
+            raise ValueError("Sizes do not match")
+        n_hat = np.ascontiguousarray(n_hat.ravel())
+        symb = np.ascontiguousarray(symb.ravel())
+        out = np.empty(n_hat.size, np.float64)
+        if n_hat.size:
+            self._device_grid()
+            check(_lib.load().qr_g_inv_host(self._h, n_hat.size, ptr(n_hat), ptr(symb), ptr(out)), "g_inv")
+        return out
+
+    def demap_lappr_simplified_array(self, n, j):
+        """noisemapper.pyx:605-620 ("Formulation 1"): LAPPRs [S*bps], out[s*bps + k] = Gray bit k
+        of symbol s, from the interpolated g_inv."""
+        n = np.asarray(n)
+        j = np.asarray(j)
+        if n.dtype != np.float64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{n.dtype}'")
+        if j.dtype != np.int64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'long' but got '{j.dtype}'")
+        if n.size != j.size:
+            raise ValueError("Sizes of transformed noise vector and tx symbols do not match")
+        n = np.ascontiguousarray(n.ravel())
+        j = np.ascontiguousarray(j.ravel())
+        out = np.empty(n.size * self.bit_per_symbol, np.float64)
+        if n.size:
+            self._device_grid()
+            check(_lib.load().qr_demap_simplified_host(self._h, n.size, ptr(n), ptr(j), ptr(out)),
+                  "demap_lappr_simplified_array")
+        return out
+
+    def demap_lappr_simplified(self, n, j):
+        """noisemapper.pyx:563-601 for one symbol."""
+        return self.demap_lappr_simplified_array(np.array([float(n)]), np.array([int(j)], np.int64))
+
     # ----------------------------------------------- Bob side (GPU, batched)
     # Single-frame (reference-style) calls: the per-symbol maps are elementwise, so one
     # frame of S symbols is laid out along the frame axis as ONE symbol row of S "frames"
@@ -335,6 +407,28 @@ class NoiseMapper:
                                                 C.c_void_p(j_fi.data_ptr()), float(alpha),
                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)),
               "demap_device")
+        return out
+
+    def demap_simplified_device(self, n_fi, j_fi, B: int, alpha: float = 1.0, out=None, stream=None):
+        """demap_device with the formulation-1 demapper (noisemapper.pyx:563-620): n_fi float64
+        [S, ld], j_fi int64 [S, ld] -> LAPPRs float64 [S*bps, ld], scaled by alpha."""
+        import torch
+
+        if not isinstance(n_fi, torch.Tensor) or n_fi.dim() != 2:
+            raise ValueError("demap_simplified_device: n_fi must be a 2-D tensor [S, ld]")
+        S, ld = n_fi.shape
+        _check_batch(B, ld, "demap_simplified_device")
+        check_tensor(n_fi, "n_fi", (S, ld), torch.float64, self._device)
+        check_tensor(j_fi, "j_fi", (S, ld), torch.int64, self._device)
+        if out is None:
+            out = torch.empty((S * self.bit_per_symbol, ld), dtype=torch.float64, device=n_fi.device)
+        check_tensor(out, "out", (S * self.bit_per_symbol, ld), torch.float64, self._device)
+        if stream is None:
+            stream = torch.cuda.current_stream(n_fi.device)
+        self._device_grid()
+        check(_lib.load().qr_demap_simplified_batch_device(
+            self._h, int(B), int(ld), int(S), C.c_void_p(n_fi.data_ptr()), C.c_void_p(j_fi.data_ptr()),
+            float(alpha), C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)), "demap_simplified_device")
         return out
 
     def bob_map_device(self, y_fi, B: int, stream=None):

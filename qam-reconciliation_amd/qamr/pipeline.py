@@ -9,7 +9,8 @@ stage is one HIP kernel of libqamr:
   channel y = a[x] + sigma * n            :132
   Bob    x_hat, n_hat, word   (k_bob)     :135-138  noisemapper.pyx:349-388
   Bob    synd = H word        (k_syndrome) :139     matrix.pyx:55-60
-  Alice  lappr = alpha * demap(n_hat, x)  :143-145  (k_demap, decoder layout)
+  Alice  lappr = alpha * demap(n_hat, x)  :143-145  (k_demap, decoder layout; or, with
+         demapper="simplified", formulation 1: k_demap_interp_wave)
   Alice  decode (k_check / k_status / k_var) :147
   count  BER/FER/iterations   (k_count_*)  :149-157
 
@@ -41,6 +42,18 @@ def alternating_config(order: int) -> np.ndarray:
     return cfg
 
 
+DEMAPPERS = ("search", "simplified")
+
+
+def check_demapper(demapper: str) -> str:
+    """The soft demapper of the softening scheme: "search" = demap_lappr_array (g_inv_search,
+    noisemapper.pyx:450-559), "simplified" = demap_lappr_simplified_array (formulation 1 on the
+    interpolated g_inv, noisemapper.pyx:563-620)."""
+    if demapper not in DEMAPPERS:
+        raise ValueError(f"demapper must be one of {DEMAPPERS}, got {demapper!r}")
+    return demapper
+
+
 def leading_dim(B: int) -> int:
     return ((B + 255) // 256) * 256 if B >= 256 else ((B + 63) // 64) * 64
 
@@ -59,7 +72,9 @@ class SofteningPipeline:
     """One GPU's share of ``simulate_softening_snr_dB`` for a batch of frames."""
 
     def __init__(self, decoder: Decoder, bps: int, snr_db: float, batch: int, alpha: float = 1.0,
-                 max_iterations: int = 50, sign_config=None, step: float = 2.0, device: int = 0):
+                 max_iterations: int = 50, sign_config=None, step: float = 2.0, device: int = 0,
+                 demapper: str = "search"):
+        self.demapper = check_demapper(demapper)
         import torch
 
         self.dec = decoder
@@ -110,6 +125,8 @@ class SofteningPipeline:
 
     # ---------------------------------------------------------- hot path
     def demap(self, batch: Batch, out=None):
+        if self.demapper == "simplified":
+            return self.nm.demap_simplified_device(batch.nhat, batch.x, batch.B, self.alpha, out=out)
         return self.nm.demap_device(batch.nhat, batch.x, batch.B, self.alpha, out=out)
 
     def decode(self, lappr_fi, batch: Batch, final=None, success=None, iters=None):

@@ -29,7 +29,7 @@ from . import _lib, dist
 from .alphabet import PAMAlphabet
 from .decoder import Decoder
 from .noisemapper import NoiseMapper
-from .pipeline import alternating_config, leading_dim
+from .pipeline import alternating_config, check_demapper, leading_dim
 
 MODES = ("softening", "direct", "hard")
 
@@ -37,7 +37,8 @@ MODES = ("softening", "direct", "hard")
 class Simulator:
     def __init__(self, decoder: Decoder, bps: int, mode: str = "softening", max_iterations: int = 50,
                  alpha: float = 1.0, batch: int = 4096, configuration_base: bool = False, step: float = 2.0,
-                 device: int = 0):
+                 device: int = 0, demapper: str = "search"):
+        self.demapper = check_demapper(demapper)   # softening mode only; the other modes have no soft demap
         import torch
 
         if mode not in MODES:
@@ -103,7 +104,10 @@ class Simulator:
         if self.mode == "softening":                       # reconciliation.pyx:129-145
             _, nhat, word = nm.bob_map_device(y, B)
             synd = self._synd(word, B, ld)
-            nm.demap_device(nhat, x, B, self.alpha, out=lappr)
+            if self.demapper == "simplified":          # noisemapper.pyx:605-620 in place of :544-559
+                nm.demap_simplified_device(nhat, x, B, self.alpha, out=lappr)
+            else:
+                nm.demap_device(nhat, x, B, self.alpha, out=lappr)
         elif self.mode == "direct":                        # reconciliation.pyx:209-221
             word = self._bits(x, B, ld)
             synd = self._synd(word, B, ld)
@@ -237,9 +241,10 @@ def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int,
 
 
 def simulate_softening_snr_dB(snr_dB, dec, bps, nmconfig, decoder_iterations, simulation_loops, ferr_count_min,
-                              alpha=1.0, batch=4096, seed=0):
-    """reconciliation.pyx:93-168 (the Matrix is the decoder's own graph)."""
-    sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch)
+                              alpha=1.0, batch=4096, seed=0, demapper="search"):
+    """reconciliation.pyx:93-168 (the Matrix is the decoder's own graph).  demapper="simplified"
+    swaps demap_lappr_array (:143) for demap_lappr_simplified_array."""
+    sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch, demapper=demapper)
     sim.cfg = np.ascontiguousarray(nmconfig, np.uint8)
     return sim.run_snr(snr_dB, simulation_loops, ferr_count_min, seed)
 

@@ -4,7 +4,7 @@ CSV schema of sim_reconciliation.py:27-102, README.md:107-145).
     PYTHONPATH=qam-reconciliation_amd python -m qamr.sim_reconciliation EDGEFILE \\
         [--out out.csv] [--maxiter 50] [--ferr-count-min 100] [--alpha 1.0] \\
         [--simloops 5000] [--snr 0 5] [--nsnr 11] [--bps 2] [--hard | --direct] \\
-        [--configuration-base] [--batch 4096] [--seed 0]
+        [--configuration-base] [--batch 4096] [--seed 0] [--demapper {search,simplified}]
 
 Instead of one OS process per SNR point (parfor), every SNR point runs batched
 on the GPU(s); launched under torchrun, each rank takes its share of every
@@ -18,7 +18,7 @@ import sys
 import numpy as np
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(prog="decode", description="Evaluate BER for LDPC codes vs Raw BER")
     p.add_argument("edgefile", help="CSV with a 'vid' and a 'cid' columns representing an edge per line")
     p.add_argument("--out", default="out.csv")
@@ -35,7 +35,14 @@ def main(argv=None):
                    help="Instead of the Alternating configuration, use the Base configuration")
     p.add_argument("--batch", type=int, default=4096, help="frames per GPU per batch")
     p.add_argument("--seed", type=int, default=0)
-    args = p.parse_args(argv)
+    p.add_argument("--demapper", choices=("search", "simplified"), default="search",
+                   help="Soft demapper of the softening scheme: the g_inv_search one, or formulation 1 on the "
+                        "interpolated g_inv")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     from . import dist
     from .codes import load_edge_csv
@@ -47,7 +54,7 @@ def main(argv=None):
     dec = Decoder(vid, cid, device=local)
     mode = "direct" if args.direct else ("hard" if args.hard else "softening")
     sim = Simulator(dec, args.bps, mode, args.maxiter, args.alpha, args.batch,
-                    configuration_base=args.configuration_base, device=local)
+                    configuration_base=args.configuration_base, device=local, demapper=args.demapper)
     rows = []
     for snr in np.linspace(args.snr[0], args.snr[1], args.nsnr):
         rows.append(sim.run_snr(float(snr), args.simloops, args.ferr_count_min, args.seed))
