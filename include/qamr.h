@@ -229,6 +229,42 @@ QR_API int qr_demap_simplified_host(const qr_demap *dm, int64_t S, const double 
 QR_API int qr_demap_simplified_batch_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, const double *d_n,
                                             const int64_t *d_j, double alpha, double *d_lappr, void *stream);
 
+/* ------------------------------ Monte-Carlo mutual information (estimator) */
+/* The tables montecarlo_information reads beside the NoiseMapper's own
+ * (mutual_information.pyx:218-224): p_xhat[M] = P_xhat(nm) (:29-39) and fwrd[M*M] =
+ * nm.fwrd_transition_probability, row-major [x][x_hat] (noisemapper.pyx:166-182).  A synchronous
+ * upload, like qr_demap_grid_create; calling it again replaces the values. */
+QR_API int qr_demap_mi_tables(qr_demap *dm, const double *p_xhat, const double *fwrd);
+/* Bytes of the per-sample term planes [3][S][ld] that qr_mi_montecarlo_device needs as workspace
+ * when the caller does not ask for the terms.  QR_EVALUE unless ld % 64 == 0, ld > 0, S >= 1. */
+QR_API int qr_mi_workspace_size(int32_t ld, int64_t S, size_t *bytes);
+/* Batched montecarlo_information (mutual_information.pyx:245-297: the loop over the N samples and
+ * the three divisions by N) on samples already drawn (:239-243 are the caller's), frame-innermost
+ * with one "frame" per call of the reference, i.e. per block of S samples:
+ *   d_x [S][ld] int64 (x_ind), d_y [S][ld] fp64 (y), B blocks in columns [0, B);
+ *   Bob's x_hat = hard_decide_index(y) and n = map_noise(y, x_hat) (:242-243) are computed inside;
+ *   d_info [3][ld] fp64: I(X;Xhat), I(X;Y), I(X,N;Xhat) of block f at d_info[q*ld + f];
+ *   d_terms [3][S][ld] fp64 or NULL: the per-sample terms log2(...) of :259, :269, :295, summed in
+ *     sample order into d_info; with NULL they live in d_workspace (qr_mi_workspace_size bytes).
+ * which_mask bit q = which[q] of the reference: a quantity whose bit is clear is not computed, its
+ * d_info is 0.0 / S and its term plane is not written.  Bit-identical to the reference for identical
+ * inputs (glibc exp / log2, the interpolated g_inv and the searched g_inv_search at 1e-9).  An x
+ * outside [0, M) gives NaN terms for that sample.  The padding columns [B, ld) are not written.
+ * QR_EVALUE: S < 1 (the reference divides by zero), B < 1, B > ld, ld % 64 != 0, a null handle, the
+ * grid (qr_demap_grid_create) or the tables (qr_demap_mi_tables) missing, a short workspace.
+ * QR_EUNSUPPORTED for bit_per_symbol > 6.  Two launches on `stream`, asynchronous, no allocation,
+ * capturable into a graph. */
+QR_API int qr_mi_montecarlo_device(const qr_demap *dm, uint32_t which_mask, int32_t B, int32_t ld, int64_t S,
+                                   const int64_t *d_x, const double *d_y, double *d_info, double *d_terms,
+                                   void *d_workspace, size_t workspace_bytes, void *stream);
+/* montecarlo_information (mutual_information.pyx:245-297) for one block of N samples from host
+ * memory: x[N], y[N], which[3] (NULL = all three), out[3], terms [3][N] or NULL.  Synchronous. */
+QR_API int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x, const double *y,
+                                 const uint8_t *which, double *out, double *terms);
+/* out[k] = log2(x[k]) by the device's restatement of glibc's log2 (mutual_information.pyx:19), host
+ * arrays of n elements, synchronous.  For tests.  Not a reference interface. */
+QR_API int qr_log2_host(int64_t n, const double *x, double *out);
+
 /* ---------------------------------------------- softening pipeline (Bob) */
 /* NoiseMapper.hard_decide_index + map_noise (noisemapper.pyx:349-388) and
  * PAMAlphabet.demap_symbols_to_bits (alphabet.pyx:98-107), fused, frame-innermost:

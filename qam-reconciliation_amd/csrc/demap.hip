@@ -15,11 +15,13 @@
 // The reference's second demapper ("Formulation 1", noisemapper.pyx:563-620) inverts F_Y by
 // interpolation in the tabulated grid instead (g_inv, :295-307): k_demap_interp_wave below, on
 // the same tiles, bound by its dependent index-search loads rather than by fp64 VALU.
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
 #include "qamr_internal.hpp"
 #include "host_build.hpp"
+#include "mi_math.hpp"
 
 namespace qr {
 
@@ -442,6 +444,8 @@ __device__ __noinline__ void dcheck_fail_demap(int site, long long a, long long 
 enum GridDebugSite {
     kDbgGridIndex = 10,    // grid index r outside [0, n), or r + 1 read with r + 1 >= n
     kDbgGridCoarse = 11,   // coarse-table index outside [0, nc)
+    kDbgMiSymbol = 12,     // k_mi_terms: the symbol index x used to read a[] / p[] / fw outside [0, M)
+    kDbgMiDecision = 13,   // k_mi_terms: Bob's hard decision x_hat outside [0, M)
 };
 
 // noisemapper.pyx:27-44 (__binsearch) over the F of the pairs, iterated: slice = [base, base + size).
@@ -616,6 +620,123 @@ __global__ void __launch_bounds__(256) k_g_inv_interp(const DemapTables *__restr
     y_hat[k] = (i < 0 || i >= t.M) ? __builtin_nan("") : grid_g_inv<FAST>(t, g, g.coarse, n_hat[k], (int)i);
 }
 
+// ---------------------------------------------------------------------------
+// Monte-Carlo mutual-information estimator (mutual_information.pyx:218-297): the three per-sample
+// terms (mi_math.hpp mi_sample_terms, the arithmetic written once) and their sequential block sums.
+// The "frame" of the frame-innermost layout is one montecarlo_information call, a block of S
+// samples: d_x[S][ld] int64 (Alice's symbol indices), d_y[S][ld] fp64 (Bob's samples), lane = block.
+//
+// k_mi_terms: one wave per (sample row s, 64-block tile), grid-stride, as k_demap_interp_wave.  A
+// lane takes Bob's hard decision x_hat and n = g(y, x_hat) for its own sample (mi_bob = k_bob's
+// expressions), then walks the hypotheses k = 0..M-1 uniformly with the interpolated g_inv; at
+// k == x_hat the root-searched y_hat is selected instead (no branch: the lanes of a wave hold
+// different x_hat).  That one search per sample is g_inv_search_wave with a per-lane hypothesis:
+// the routine is documented for a wave-uniform i, but i enters it only through search_target and
+// newton_root, both per-lane computations (k_g_inv_search already runs them with a per-lane i);
+// the wave-cooperative part -- compaction of the lanes' evaluation points, M erf terms per point,
+// the owner's sum in m order -- reads t.a / t.p / t.den and the lane's own target, never i.  What it
+// does need is that every lane of the wave calls it, which holds here (padding lanes run a harmless
+// sample).  Terms go to d_terms[q][s][ld], q = 0..2; planes of disabled quantities and the padding
+// columns are not written; an out-of-range x gives NaN terms for that sample.
+struct MiLds {
+    double2 ex[128];   // glibc exp table (g_exp_wave / g_exp_full read T.ex)
+    double4 e[64];     // glibc log2 table (g_log2_full reads T.e)
+};
+template <int BPS, bool FAST>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))
+k_mi_terms(const DemapTables *__restrict__ tab, const MathTables *__restrict__ gmt, const GridView g,
+           const double *__restrict__ mi, unsigned which, int B, int ld, int64_t S, const int64_t *__restrict__ x,
+           const double *__restrict__ y, double *__restrict__ terms) {
+    constexpr int M = 1 << BPS;
+    __shared__ MiLds lt;
+    __shared__ double ey[4][64], et[4][64];
+    extern __shared__ double coarse[];   // FAST: g.nc entries
+    for (int i = threadIdx.x; i < 128; i += blockDim.x) lt.ex[i] = kGlibcConst.ex[i];
+    for (int i = threadIdx.x; i < 64; i += blockDim.x) lt.e[i] = kGlibcLog2Const.e[i];
+    if (FAST)
+        for (int c = threadIdx.x; c < g.nc; c += blockDim.x) coarse[c] = g.coarse[c];
+    __syncthreads();
+    const DemapTables &t = *tab;
+    const double *pX = mi, *fw = mi + M;   // qr_demap_mi_tables: p_Xhat[M] then fwrd[M][M]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t tiles = ld / 64;
+    const int64_t items = S * tiles;
+    for (int64_t it = (int64_t)blockIdx.x * 4 + w; it < items; it += (int64_t)gridDim.x * 4) {   // wave-uniform
+        const int64_t s = it / tiles;
+        const int f = (int)(it - s * tiles) * 64 + lane;
+        const bool valid = f < B;
+        const double yv = valid ? y[s * ld + f] : 0.25;   // padding lanes: a harmless sample
+        const int64_t xv = valid ? x[s * ld + f] : 0;
+        const bool xok = xv >= 0 && xv < M;
+        const int xx = xok ? (int)xv : 0;
+        int xh;
+        double nv;
+        mi_bob(t, yv, xh, nv);
+        QR_DCHECK(xx >= 0 && xx < M, kDbgMiSymbol, xx, M);
+        QR_DCHECK(xh >= 0 && xh < M, kDbgMiDecision, xh, M);
+        double ys = 0.0;
+        if (which & kMiXNXhat) ys = g_inv_search_wave<M>(t, *gmt, nv, xh, ey[w], et[w], lane);   // wave-uniform branch
+        mi_sample_terms(
+            t, pX, fw, M, which, xx, xh, yv,
+            [&](int k) { const double yi = grid_g_inv<FAST>(t, g, coarse, nv, k); return k == xh ? ys : yi; },
+            [&](double a) { return g_exp_wave(a, lt); }, [&](double a) { return g_log2_full(a, lt); },
+            [&](int q, double v) { if (valid) terms[((int64_t)q * S + s) * ld + f] = xok ? v : __builtin_nan(""); });
+    }
+}
+
+// k_mi_sum: the block totals (mutual_information.pyx:245-297).  One lane per (block, quantity): it
+// adds (I0, I1) or subtracts (I2) its S terms in sample order from 0.0 and divides by (double)S; a
+// disabled quantity is 0.0 / S.  The chain of dependent adds cannot be reordered, so the launch has
+// 3 B lanes of parallelism whatever S is: the next kMiSumAhead rows are requested before the current
+// kMiSumAhead are added, so the chain does not wait for memory (S = 4096, B = 256: 0.184 ms with 8 rows
+// loaded right before their adds, 0.127 ms now; profiles/mi/README.md).
+constexpr int kMiSumAhead = 32;
+// the chain of one (block, quantity): SUB subtracts (I2, :295), else adds (:259, :269); a template so
+// that the dependent chain is one v_add_f64 per sample, not both results and a select
+template <bool SUB>
+__device__ __forceinline__ double mi_chain(const double *__restrict__ p, int ld, int64_t S) {
+    double acc = 0.0;
+    double v[kMiSumAhead], nx[kMiSumAhead];
+    int64_t s = 0;
+    if (S >= kMiSumAhead) {
+#pragma unroll
+        for (int u = 0; u < kMiSumAhead; ++u) v[u] = p[u * (int64_t)ld];
+    }
+    for (; s + kMiSumAhead <= S; s += kMiSumAhead) {
+        const bool more = s + 2 * kMiSumAhead <= S;   // block-uniform
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < kMiSumAhead; ++u) nx[u] = p[(s + kMiSumAhead + u) * ld];
+        }
+#pragma unroll
+        for (int u = 0; u < kMiSumAhead; ++u) acc = SUB ? acc - v[u] : acc + v[u];
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < kMiSumAhead; ++u) v[u] = nx[u];
+        }
+    }
+    for (; s < S; ++s) acc = SUB ? acc - p[s * ld] : acc + p[s * ld];
+    return acc;
+}
+__global__ void __launch_bounds__(64) k_mi_sum(unsigned which, int B, int ld, int64_t S,
+                                               const double *__restrict__ terms, double *__restrict__ info) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    const int q = blockIdx.y;
+    if (f >= B) return;
+    double acc = 0.0;
+    if ((which >> q) & 1u) {
+        const double *p = terms + (int64_t)q * S * ld + f;
+        acc = q == 2 ? mi_chain<true>(p, ld, S) : mi_chain<false>(p, ld, S);   // block-uniform
+    }
+    info[(int64_t)q * ld + f] = acc / (double)S;
+}
+
+// glibc log2 over an array (qr_log2_host)
+__global__ void __launch_bounds__(256) k_log2(int64_t n, const double *__restrict__ x, double *__restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) out[k] = g_log2_full(x[k], kGlibcLog2Const);
+}
+
 // The grid itself (noisemapper.pyx:143-144): y[i] as numpy's linspace computes it,
 // fl(fl(i * step) + y_low) with the last point set to y_high, and F = the cpdef F_Y of it.
 __global__ void __launch_bounds__(256) k_grid_build(const DemapTables *__restrict__ tab, int32_t n, double y_low,
@@ -756,6 +877,46 @@ int demap_simplified_batch_device(const qr_demap *dm, int B, int ld, int64_t S, 
     return QR_OK;
 }
 
+template <bool FAST>
+static bool launch_mi_terms(int bps, unsigned grid, size_t lds, hipStream_t st, const qr_demap *dm, const GridView &g,
+                            unsigned which, int B, int ld, int64_t S, const int64_t *x, const double *y, double *terms) {
+    switch (bps) {
+#define QR_MI_TERMS(b) \
+        case b: k_mi_terms<b, FAST><<<grid, 256, lds, st>>>(dm->d_tables, dm->d_mtab, g, dm->d_mi, which, B, ld, S, x, y, terms); return true;
+        QR_MI_TERMS(1) QR_MI_TERMS(2) QR_MI_TERMS(3) QR_MI_TERMS(4) QR_MI_TERMS(5) QR_MI_TERMS(6)
+#undef QR_MI_TERMS
+        default: return false;
+    }
+}
+
+// the two launches of the estimator on stream s; the checks are the caller's
+static int mi_launch(const qr_demap *dm, unsigned which, int B, int ld, int64_t S, const int64_t *x, const double *y,
+                     double *info, double *terms, hipStream_t s) {
+    const GridView gv = grid_view(dm);
+    {
+        ProfScope ps("mi_terms", s);
+        const int64_t items = S * (ld / kWave);
+        const unsigned grid = demap_wave_grid(dm->device, (items + 3) / 4);
+        if (grid_fast(dm))   // nc <= kGridMaxCoarse by construction
+            launch_mi_terms<true>(dm->h.bps, grid, (size_t)gv.nc * sizeof(double), s, dm, gv, which, B, ld, S, x, y, terms);
+        else
+            launch_mi_terms<false>(dm->h.bps, grid, 0, s, dm, gv, which, B, ld, S, x, y, terms);
+        QR_LAUNCH_CHECK();
+    }
+    if (info) {
+        ProfScope ps("mi_sum", s);
+        k_mi_sum<<<dim3((unsigned)(ld / kWave), 3), 64, 0, s>>>(which, B, ld, S, terms, info);
+        QR_LAUNCH_CHECK();
+    }
+    return QR_OK;
+}
+
+static int mi_ready(const qr_demap *dm) {
+    if (dm->grid.n <= 0) return set_error(QR_EVALUE, "the interpolation grid has not been created (qr_demap_grid_create)");
+    if (!dm->d_mi) return set_error(QR_EVALUE, "the mutual-information tables have not been created (qr_demap_mi_tables)");
+    return QR_OK;
+}
+
 #if QR_DEBUG_ASSERT
 int debug_asserts_demap(unsigned long long h[4]) {
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dbg_demap), 4 * sizeof(unsigned long long)) != hipSuccess) return QR_EDEVICE;
@@ -848,6 +1009,7 @@ int qr_demap_destroy(qr_demap *dm) {
         (void)hipFree(dm->d_ftab);
         (void)hipFree(dm->grid.d_pairs);
         (void)hipFree(dm->grid.d_coarse);
+        (void)hipFree(dm->d_mi);
     }
     delete dm;
     return QR_OK;
@@ -992,6 +1154,107 @@ int qr_demap_simplified_batch_device(const qr_demap *dm, int32_t B, int32_t ld, 
                                      const int64_t *d_j, double alpha, double *d_lappr, void *stream) {
     if (!dm) return set_error(QR_EVALUE, "null demapper");
     return demap_simplified_batch_device(dm, B, ld, S, d_n, d_j, alpha, d_lappr, (hipStream_t)stream);
+}
+
+// ---- Monte-Carlo mutual information (mutual_information.pyx:218-297) ----
+int qr_demap_mi_tables(qr_demap *dm, const double *p_xhat, const double *fwrd) {
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (!p_xhat || !fwrd) return set_error(QR_EVALUE, "null pointer argument");
+    const size_t M = (size_t)dm->h.M, n = M + M * M;
+    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    DeviceGuard g(dm->device);
+    if (!dm->d_mi) QR_HIP(hipMalloc((void **)&dm->d_mi, n * sizeof(double)));
+    QR_HIP(hipDeviceSynchronize());   // a replacement: no launch that reads the old values is pending
+    QR_HIP(hipMemcpy(dm->d_mi, p_xhat, M * sizeof(double), hipMemcpyHostToDevice));
+    QR_HIP(hipMemcpy(dm->d_mi + M, fwrd, M * M * sizeof(double), hipMemcpyHostToDevice));
+    return QR_OK;
+}
+
+int qr_mi_workspace_size(int32_t ld, int64_t S, size_t *bytes) {
+    if (!bytes) return set_error(QR_EVALUE, "null output pointer");
+    *bytes = 0;
+    if (int rc = check_shape(ld > 0 ? ld : 1, ld, S)) return rc;
+    *bytes = align_up((size_t)3 * (size_t)S * (size_t)ld * sizeof(double), 256);
+    return QR_OK;
+}
+
+int qr_mi_montecarlo_device(const qr_demap *dm, uint32_t which_mask, int32_t B, int32_t ld, int64_t S,
+                            const int64_t *d_x, const double *d_y, double *d_info, double *d_terms, void *d_workspace,
+                            size_t workspace_bytes, void *stream) {
+    if (int rc = check_shape(B, ld, S)) return rc;   // S < 1: the reference divides by zero
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (which_mask & ~kMiAll) return set_error(QR_EVALUE, "which_mask has bits beyond the three quantities");
+    if (!d_x || !d_y || !d_info) return set_error(QR_EVALUE, "null pointer argument");
+    if (int rc = mi_ready(dm)) return rc;
+    if (dm->h.bps > kDemapWaveMaxBps)
+        return set_error(QR_EUNSUPPORTED, "the batched estimator serves bit_per_symbol <= %d (got %d)", kDemapWaveMaxBps,
+                         dm->h.bps);
+    if (!d_terms) {
+        size_t need = 0;
+        (void)qr_mi_workspace_size(ld, S, &need);
+        if (!d_workspace || workspace_bytes < need)
+            return set_error(QR_EVALUE, "workspace too small: %zu bytes, need %zu (qr_mi_workspace_size)", workspace_bytes,
+                             need);
+        d_terms = (double *)d_workspace;
+    }
+    DeviceGuard g(dm->device);
+    return mi_launch(dm, which_mask, B, ld, S, d_x, d_y, d_info, d_terms, (hipStream_t)stream);
+}
+
+// One block from host memory.  The per-sample kernel is elementwise, so the N samples are laid
+// along the frame axis as ONE sample row of N "blocks" (S = 1, ld = N rounded up to 64); the
+// block's own sums (:245-297) are then taken here, in sample order, on the terms copied back.
+int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x, const double *y, const uint8_t *which,
+                          double *out, double *terms) {
+    if (N < 1) return set_error(QR_EVALUE, "N must be positive (the reference divides by N)");
+    if (N > (int64_t)1 << 30) return set_error(QR_EVALUE, "N too large for one host block");
+    if (!dm) return set_error(QR_EVALUE, "null demapper");
+    if (!x || !y || !out) return set_error(QR_EVALUE, "null pointer argument");
+    if (int rc = mi_ready(dm)) return rc;
+    if (dm->h.bps > kDemapWaveMaxBps)
+        return set_error(QR_EUNSUPPORTED, "the estimator serves bit_per_symbol <= %d (got %d)", kDemapWaveMaxBps, dm->h.bps);
+    const unsigned mask = which ? (which[0] ? kMiXXhat : 0u) | (which[1] ? kMiXY : 0u) | (which[2] ? kMiXNXhat : 0u) : kMiAll;
+    const int ld = (int)align_up((size_t)N, kWave);
+    DeviceGuard g(dm->device);
+    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    int64_t *d_x;
+    double *d_y, *d_t;
+    if (int rc = dm->scratch.take(&d_x, (size_t)ld, &d_y, (size_t)ld, &d_t, (size_t)3 * ld)) return rc;
+    QR_HIP(hipMemcpy(d_x, x, (size_t)N * 8, hipMemcpyHostToDevice));
+    QR_HIP(hipMemcpy(d_y, y, (size_t)N * 8, hipMemcpyHostToDevice));
+    if (int rc = mi_launch(dm, mask, (int)N, ld, 1, d_x, d_y, nullptr, d_t, nullptr)) return rc;
+    std::vector<double> h((size_t)N);
+    for (int q = 0; q < 3; ++q) {
+        double acc = 0.0;
+        if ((mask >> q) & 1u) {
+            QR_HIP(hipMemcpy(h.data(), d_t + (size_t)q * ld, (size_t)N * 8, hipMemcpyDeviceToHost));
+            for (int64_t p = 0; p < N; ++p) acc = q == 2 ? acc - h[(size_t)p] : acc + h[(size_t)p];
+        } else {
+            std::fill(h.begin(), h.end(), 0.0);
+        }
+        if (terms) memcpy(terms + (size_t)q * N, h.data(), (size_t)N * 8);
+        out[q] = acc / (double)N;
+    }
+    return QR_OK;
+}
+
+int qr_log2_host(int64_t n, const double *x, double *out) {
+    if (n < 0) return set_error(QR_EVALUE, "negative size");
+    if (n == 0) return QR_OK;
+    if (!x || !out) return set_error(QR_EVALUE, "null pointer argument");
+    double *d_x = nullptr, *d_o = nullptr;
+    hipError_t e = hipMalloc((void **)&d_x, (size_t)n * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_o, (size_t)n * 8);
+    if (e == hipSuccess) e = hipMemcpy(d_x, x, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        k_log2<<<(unsigned)((n + 255) / 256), 256>>>(n, d_x, d_o);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_o, (size_t)n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_x);
+    (void)hipFree(d_o);
+    if (e != hipSuccess) return hip_fail(e, "qr_log2_host", __FILE__, __LINE__);
+    return QR_OK;
 }
 
 int qr_demap_tables(const qr_demap *dm, double *Fthr, double *dF) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate glibc_tables.inc: the data of the host libm's exp() and log().
+"""Generate glibc_tables.inc: the data of the host libm's exp(), log() and log2().
 
 The reference's box-plus (decoder.pyx:41-45) calls glibc's exp and log; on x86-64
 with FMA, glibc 2.35 dispatches them (ifunc) to __exp_fma / __log_fma, compiled from
@@ -34,6 +34,37 @@ def _find_unique(data, pat, what):
 
 def hexd(x):
     return float.hex(x)
+
+
+def log2_lines(data):
+    """struct log2_data {invln2hi, invln2lo, poly[6], poly1[10], tab[64] {invc, logc}, tab2[64] {chi, clo}}
+    of sysdeps/ieee754/dbl-64/e_log2_data.c: the build without __FP_FAST_FMA (invln2hi has its low
+    32 bits clear and tab2 is present), which is what libm's log2 symbol is on x86-64 (no ifunc
+    variant; glibc_math.hpp g_log2_full).  New names only: everything above stays as it was."""
+    o = _find_unique(data, struct.pack("<dd", float.fromhex("0x1.7154765200000p+0"),
+                                       float.fromhex("0x1.705fc2eefa200p-33")), "log2_data")
+    head = struct.unpack_from("<18d", data, o)
+    tab = struct.unpack_from("<128d", data, o + 18 * 8)
+    tab2 = struct.unpack_from("<128d", data, o + (18 + 128) * 8)
+    # sanity: invc in (0.5, 2), chi = the centre c ~ 1 / invc and |clo| far below it, the first polynomials'
+    # leading coefficients -1/(2 ln 2)
+    ok = all(0.5 < tab[2 * i] < 2.0 and abs(tab2[2 * i] * tab[2 * i] - 1.0) < 1e-3 and abs(tab2[2 * i + 1]) < 1e-15
+             for i in range(64))
+    if not ok or abs(head[2] + 0.7213475204444817) > 1e-9 or abs(head[8] + 0.7213475204444817) > 1e-9:
+        raise SystemExit("gen_glibc_tables: unexpected log2 table contents (not glibc 2.28+ non-FMA log2_data)")
+    L = ["// glibc log2_data (e_log2_data.c, the build without __FP_FAST_FMA), see glibc_math.hpp g_log2_full.",
+         f"constexpr double kGl2InvLn2hi = {hexd(head[0])};", f"constexpr double kGl2InvLn2lo = {hexd(head[1])};"]
+    for i in range(6):
+        L.append(f"constexpr double kGl2A{i} = {hexd(head[2 + i])};")
+    for i in range(10):
+        L.append(f"constexpr double kGl2B{i} = {hexd(head[8 + i])};")
+    L.append("// log2: {invc, logc, chi, clo} for i = 0..63 (tab and tab2 of log2_data); the initializer of qr::GlibcLog2")
+    L.append("#define QR_GLIBC_LOG2_INIT { { \\")
+    for i in range(64):
+        L.append("        {" + ", ".join(hexd(v) for v in (tab[2 * i], tab[2 * i + 1], tab2[2 * i], tab2[2 * i + 1])) +
+                 "}, \\")
+    L.append("    } }")
+    return L
 
 
 def main():
@@ -107,6 +138,7 @@ def main():
     for i in range(0, 128, 2):
         L.append("        " + " ".join(f"{{{hexd(ltab[2 * k])}, {hexd(ltab[2 * k + 1])}}}," for k in (i, i + 1)) + " \\")
     L.append("    } }")
+    L += log2_lines(data)
     open(out, "w").write("\n".join(L) + "\n")
 
 

@@ -339,6 +339,76 @@ __host__ __device__ __forceinline__ double g_log_full(double x, const TT &T) {
 // (the rare erfc exp of the demapper's exact F_Y evaluations).
 __constant__ static const GlibcTables kGlibcConst = QR_GLIBC_TABLES_INIT;
 
+// ---- log2 (the mutual-information estimator: mutual_information.pyx:19, :259-295) --------
+//
+// libm's log2 on x86-64 is ONE routine, sysdeps/ieee754/dbl-64/e_log2.c compiled without FMA
+// (the symbol is a plain function, there is no ifunc variant of it; its disassembly holds only
+// mulsd / addsd / subsd and reads log2_data's tab2, which exists only without __FP_FAST_FMA):
+// every operation below is a separately rounded IEEE operation in e_log2.c's order, r split
+// into rhi (the high 32 bits of its pattern) and rlo instead of the FMA variant's exact products.
+//   x in [1 - 0x1.5b51p-5, 1 + 0x1.6ab2p-5): the degree-11 polynomial in r = x - 1 (poly1, B);
+//   otherwise: i, k from the top bits of x - OFF (64 intervals), r = (z - chi_i - clo_i) invc_i,
+//     t3 = k + logc_i, hi = t3 + rhi InvLn2hi, lo = t3 - hi + t1 + t2,
+//     log2 = lo + r^2 (A0 + r A1 + r^2 (A2 + r A3) + r^4 (A4 + r A5)) + hi;
+//   0 -> -inf, +inf -> +inf, negative or NaN -> NaN, subnormals rescaled by 2^52.
+// tests/native/mi_check.cpp compares it with libm's log2 on > 16 M inputs, bit for bit.
+struct GlibcLog2 {
+    double4 e[64];   // {invc, logc, chi, clo}: tab[i] and tab2[i] of log2_data
+};
+__constant__ static const GlibcLog2 kGlibcLog2Const = QR_GLIBC_LOG2_INIT;
+#if !defined(__HIP_DEVICE_COMPILE__)
+static const GlibcLog2 kGlibcLog2Host = QR_GLIBC_LOG2_INIT;   // the same data for host callers
+#endif
+
+template <class TT>   // TT: anything with the member e[64] of GlibcLog2
+__host__ __device__ __forceinline__ double g_log2_full(double x, const TT &T) {
+#pragma clang fp contract(off)
+    uint64_t ix = __builtin_bit_cast(uint64_t, x);
+    const uint32_t top = (uint32_t)(ix >> 48);
+    if (ix - 0x3FEEA4AF00000000ull < 0x000210AA00000000ull) {   // asuint64(1 + 0x1.6ab2p-5) - LO
+        if (ix == 0x3FF0000000000000ull) return 0.0;
+        const double r = x - 1.0;
+        const double rhi = __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, r) & 0xFFFFFFFF00000000ull);
+        const double rlo = r - rhi;
+        const double hi = rhi * kGl2InvLn2hi;
+        double lo = rlo * kGl2InvLn2hi + r * kGl2InvLn2lo;
+        const double r2 = r * r;
+        const double r4 = r2 * r2;
+        const double p = r2 * (kGl2B0 + r * kGl2B1);
+        double y = hi + p;
+        lo += hi - y + p;
+        lo += r4 * (kGl2B2 + r * kGl2B3 + r2 * (kGl2B4 + r * kGl2B5) +
+                    r4 * (kGl2B6 + r * kGl2B7 + r2 * (kGl2B8 + r * kGl2B9)));
+        y += lo;
+        return y;
+    }
+    if (top - 0x0010u >= 0x7FF0u - 0x0010u) {
+        if (ix * 2 == 0) return -__builtin_inf();
+        if (ix == 0x7FF0000000000000ull) return x;
+        if ((top & 0x8000u) || (top & 0x7FF0u) == 0x7FF0u) return __builtin_nan("");
+        ix = __builtin_bit_cast(uint64_t, x * 0x1p52);   // subnormal
+        ix -= 52ull << 52;
+    }
+    const uint64_t tmp = ix - 0x3FE6000000000000ull;   // OFF
+    const int i = (int)(tmp >> 46) & 63;
+    const int k = (int)((int64_t)tmp >> 52);
+    const double z = __builtin_bit_cast(double, ix - (tmp & 0xFFF0000000000000ull));
+    const double4 c = T.e[i];
+    const double kd = (double)k;
+    const double r = (z - c.z - c.w) * c.x;
+    const double rhi = __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, r) & 0xFFFFFFFF00000000ull);
+    const double rlo = r - rhi;
+    const double t1 = rhi * kGl2InvLn2hi;
+    const double t2 = rlo * kGl2InvLn2hi + r * kGl2InvLn2lo;
+    const double t3 = kd + c.y;
+    const double hi = t3 + t1;
+    const double lo = t3 - hi + t1 + t2;
+    const double r2 = r * r;
+    const double r4 = r2 * r2;
+    const double p = kGl2A0 + r * kGl2A1 + r2 * (kGl2A2 + r * kGl2A3) + r4 * (kGl2A4 + r * kGl2A5);
+    return lo + r2 * p + hi;
+}
+
 // ---- the box-plus domain: h(t) = log(1.0 + exp(-t)), t >= 0, inf or NaN ----------------
 //
 // GlibcK: the addends of the fmas whose two other operands are constants too.  gfx9

@@ -214,5 +214,6 @@ struct qr_demap {
     qr::MathTables *d_mtab = nullptr;       // exp table for the Newton root search
     double2 *d_quant = nullptr;             // F_Y^-1 Hermite nodes (Newton start), may be null
     double *d_ftab = nullptr;               // Taylor table of F_Y (Newton), may be null
+    double *d_mi = nullptr;                 // p_Xhat[M] then fwrd_transition_probability[M][M] (qr_demap_mi_tables)
     mutable qr::Scratch scratch;
 };

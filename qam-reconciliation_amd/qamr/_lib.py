@@ -60,6 +60,11 @@ SIGNATURES = {
     "qr_g_inv_host": [vp, i64, vp, vp, vp],
     "qr_demap_simplified_host": [vp, i64, vp, vp, vp],
     "qr_demap_simplified_batch_device": [vp, i32, i32, i64, vp, vp, f64, vp, vp],
+    "qr_demap_mi_tables": [vp, vp, vp],
+    "qr_mi_workspace_size": [i32, i64, P(C.c_size_t)],
+    "qr_mi_montecarlo_device": [vp, C.c_uint32, i32, i32, i64, vp, vp, vp, vp, vp, C.c_size_t, vp],
+    "qr_mi_montecarlo_host": [vp, i64, vp, vp, vp, vp, vp],
+    "qr_log2_host": [i64, vp, vp],
     "qr_bob_map_device": [vp, i32, i32, i64, vp, vp, vp, vp, vp],
     "qr_map_noise_device": [vp, i32, i32, i64, vp, vp, vp, vp],
     "qr_syndrome_device": [vp, i32, i32, vp, vp, vp],
