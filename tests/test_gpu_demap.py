@@ -193,8 +193,8 @@ def test_wave_private_demap_equals_per_symbol(gpu, bps, snr):
     """The wave-private demapper (default on 64-frame tiles: one wave walks all hypotheses of its
     tile, cooperative exact F_Y, Gray sums in i order in LDS) returns the per-symbol
     kernel's doubles bit for bit, on a ragged batch (B < ld) with out-of-range symbol
-    indices (-> NaN) and both sign configurations; and its 2..16-PAM output matches the
-    oracle (reference restatement) on sampled frames."""
+    indices (-> NaN) and both sign configurations; and its output matches the oracle
+    (reference restatement) on sampled frames."""
     import torch
     from qamr import _lib
 
@@ -226,11 +226,13 @@ def test_wave_private_demap_equals_per_symbol(gpu, bps, snr):
     same = (a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))
     assert same.all(), f"{(~same).sum()} LAPPRs differ"
     assert np.isnan(a[bps:2 * bps, :3]).all()
-    if bps <= 4:
-        onm = O.OracleNoiseMapper(bps, 2.0, nv, cfg)
-        for f in (0, 63, 64, B - 1):
-            ref = onm.demap_lappr_array(n[2:, f].copy(), x[2:, f].copy()) * 0.5
-            assert_bit_exact(a[2 * bps:, f], ref)
+    onm = O.OracleNoiseMapper(bps, 2.0, nv, cfg)
+    # 32 / 64-PAM (the oracle is pinned on them by tests/test_demap_wide_cpu.py) on fewer points: the
+    # oracle's brute-force search costs M^2 erf per step
+    frames, last = ((0, 63, 64, B - 1), S) if bps <= 4 else ((0, B - 1), 2 + 64)
+    for f in frames:
+        ref = onm.demap_lappr_array(n[2:last, f].copy(), x[2:last, f].copy()) * 0.5
+        assert_bit_exact(a[2 * bps:last * bps, f], ref)
 
 
 # --------------------------------------- F_Y / g / g_inv_search surface (noisemapper.pyx:264-419)
