@@ -265,6 +265,59 @@ QR_API int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x
  * arrays of n elements, synchronous.  For tests.  Not a reference interface. */
 QR_API int qr_log2_host(int64_t n, const double *x, double *out);
 
+/* ------------------------------ quad-integrated mutual information */
+/* mutual_information_base_scheme (mutual_information.pyx:123-148, kind 0: the integral of
+ * mutual_information_base_scheme_arg, :43-119, over [0, 1]) and mutual_information_X_Y (:202-208, kind 1:
+ * the integral of mutual_information_X_Y_int_arg, :175-199, over (-inf, inf)) as scipy.integrate.quad
+ * computes them: QUADPACK's QAGS / QAGI restated operation by operation, the integrands evaluated on
+ * the GPU with glibc's exp / log2 and the interpolated g_inv.  P integrals ("problems") in one call:
+ *   dms [P]: the problem's demapper (all of one bit_per_symbol <= 6 and one device, each with its grid,
+ *     qr_demap_grid_create; the same handle may appear many times);
+ *   p_xhat [P][M] (host; kind 0 only, NULL otherwise): P_xhat of each problem (:29-39);
+ *   sign_cfg [P][M] (host) or NULL: each problem's sign configuration instead of its handle's (it enters
+ *     only g_inv's target, noisemapper.pyx:297-307, so one handle per noise variance serves every
+ *     configuration);
+ *   epsabs, epsrel, limit: quad's arguments (its defaults: 1.49e-8, 1.49e-8, 50);
+ *   result, abserr, neval, ier [P] (host): quad's I, its error estimate, infodict["neval"], and QUADPACK's
+ *     ier; any non-zero ier is one of the cases in which scipy warns (6 also for QUADPACK's own refusal
+ *     of epsabs <= 0 with epsrel < max(50 eps, 0.5e-28)).
+ * Bit-identical to the reference for identical inputs, the integrals it returns as -inf included; a
+ * problem's results do not depend on what else is in the batch.  Round r evaluates the pending rule(s)
+ * of every unfinished problem in one launch on `stream` and copies 8 doubles per problem back; the
+ * integrator's decisions are taken on the calling thread in between, so the call is synchronous, ends
+ * after at most `limit` rounds, allocates its device buffers itself and cannot be captured into a graph.
+ * QR_EVALUE: P < 0, limit < 1, a kind other than 0 / 1, a null handle or output, handles of different
+ * bit_per_symbol or device, a missing grid, kind 0 without p_xhat.  QR_EUNSUPPORTED for
+ * bit_per_symbol > 6. */
+QR_API int qr_mi_quad_batch(const qr_demap *const *dms, const double *p_xhat, const uint8_t *sign_cfg, int32_t P,
+                            int32_t kind, double epsabs, double epsrel, int32_t limit, double *result, double *abserr,
+                            int32_t *neval, int32_t *ier, void *stream);
+/* out[5] = {rounds, launches, work items, ns of host bookkeeping, ns in all} of the calling thread's last
+ * qr_mi_quad_batch.  For measurement.  Not a reference interface. */
+QR_API int qr_mi_quad_stats(int64_t *out);
+/* The integrands themselves over arrays: f[k] = mutual_information_base_scheme_arg(x[k], nm, p_Xhat)
+ * (kind 0; p_Xhat as given to qr_demap_mi_tables) or mutual_information_X_Y_int_arg(x[k], nm) (kind 1),
+ * with the handle's own sign configuration.  Device arrays, one launch on `stream`, asynchronous,
+ * capturable; the host version copies in, launches once and copies out.  The grid must exist. */
+QR_API int qr_mi_integrand_device(const qr_demap *dm, int32_t kind, int64_t n, const double *d_x, double *d_f,
+                                  void *stream);
+QR_API int qr_mi_integrand_host(const qr_demap *dm, int32_t kind, int64_t n, const double *x, double *f);
+/* One work item of the batch's kernel with its debug pointer, for tests: the rule(s) of `nh` (1 or 2)
+ * intervals [a[h], b[h]] of one problem (kind 0: the 21-point rule on the interval; kind 1: the
+ * transformed 15-point rule, the interval within (0, 1]); p_xhat [M] (host, kind 0), sign_cfg [M] or NULL.
+ * sums [nh][4] = {result, |(resk - resg) hlgth|, resabs, resasc} as the kernel leaves them (the pow step of
+ * the error estimate is the host's); nodes [nh][21][2] (kind 0) or [nh][30][2] (kind 1), or NULL: each lane's
+ * {abscissa, integrand value}, kind 0 in node order (the centre, the 10 nodes below it outermost first, the
+ * 10 above it), kind 1 as pairs (+T, -T) per node.  Synchronous.  Not a reference interface. */
+QR_API int qr_mi_quad_rule_host(const qr_demap *dm, const double *p_xhat, const uint8_t *sign_cfg, int32_t kind,
+                                int32_t nh, const double *a, const double *b, double *sums, double *nodes);
+/* The integrator alone over a C callback, on the host (no device call), for tests: kind 0 is
+ * quad(f, a, b), kind 1 quad(f, -inf, inf) (a, b ignored); `last` is infodict["last"].  Outputs may be
+ * NULL.  QR_EVALUE for a null f, limit < 1 or another kind.  Not a reference interface. */
+typedef double (*qr_quad_fn)(double x, void *user);
+QR_API int qr_quad_host(qr_quad_fn f, void *user, int32_t kind, double a, double b, double epsabs, double epsrel,
+                        int32_t limit, double *result, double *abserr, int32_t *neval, int32_t *ier, int32_t *last);
+
 /* ---------------------------------------------- softening pipeline (Bob) */
 /* NoiseMapper.hard_decide_index + map_noise (noisemapper.pyx:349-388) and
  * PAMAlphabet.demap_symbols_to_bits (alphabet.pyx:98-107), fused, frame-innermost:

@@ -125,6 +125,7 @@ inline int build_demap_host(int32_t bps, const double *constellation, const doub
     t.den = sqrt(2.0) * sigma;                                // __sqrt2 * sigma (:24, :67)
     t.two_s2 = 2 * noise_var;                                 // :469
     t.inv_two_s2 = 1.0 / t.two_s2;                            // div_two_s2
+    t.mi_norm = sqrt(2.0 * 3.141592653589793) * sigma;        // mutual_information.pyx:198 (np.pi)
     t.Fthr[0] = 0;                                            // :149-153
     t.Fthr[M] = 1;
     for (int i = 1; i < M; ++i) t.Fthr[i] = single_F_Y(t, t.thr[i]);

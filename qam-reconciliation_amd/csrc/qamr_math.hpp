@@ -131,6 +131,7 @@ struct DemapTables {
     int32_t ftab_n;
     double ftab_lo, ftab_inv_w, ftab_h, ftab_inv_h, ftab_err;
     const double2 *quant;       // [M][kQStride] F_Y^-1 Hermite nodes (Newton start), see build_quantiles
+    double mi_norm;             // sqrt(2.0 * pi) * noise_sigma (mutual_information.pyx:198, mi_math.hpp mi_xy_arg)
 };
 
 // Newton start table, per decision region k: nodes (y, dy/dx) of y = F_Y^-1(F_thr[k] + u dF[k])

@@ -65,6 +65,12 @@ SIGNATURES = {
     "qr_mi_montecarlo_device": [vp, C.c_uint32, i32, i32, i64, vp, vp, vp, vp, vp, C.c_size_t, vp],
     "qr_mi_montecarlo_host": [vp, i64, vp, vp, vp, vp, vp],
     "qr_log2_host": [i64, vp, vp],
+    "qr_mi_quad_batch": [vp, vp, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp],
+    "qr_mi_quad_stats": [vp],
+    "qr_mi_quad_rule_host": [vp, vp, vp, i32, i32, vp, vp, vp, vp],
+    "qr_mi_integrand_device": [vp, i32, i64, vp, vp, vp],
+    "qr_mi_integrand_host": [vp, i32, i64, vp, vp],
+    "qr_quad_host": [vp, vp, i32, f64, f64, f64, f64, i32, P(f64), P(f64), P(i32), P(i32), P(i32)],
     "qr_bob_map_device": [vp, i32, i32, i64, vp, vp, vp, vp, vp],
     "qr_map_noise_device": [vp, i32, i32, i64, vp, vp, vp, vp],
     "qr_syndrome_device": [vp, i32, i32, vp, vp, vp],
@@ -80,6 +86,7 @@ SIGNATURES = {
     "qr_clock_probe": [vp, i32, i64, vp],
 }
 _RESTYPE = {"qr_last_error": C.c_char_p}
+QUAD_FN = C.CFUNCTYPE(f64, f64, vp)   # qr_quad_fn
 
 
 class QamrError(RuntimeError):

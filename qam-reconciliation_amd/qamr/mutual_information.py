@@ -11,8 +11,13 @@ draws, ``y = a[x] + sigma * z`` -- and evaluates the block on the GPU (qr_mi_mon
 ``np.random.seed(s)`` it returns the doubles the reference returns.  ``montecarlo_information_device``
 evaluates B such blocks, already in HBM, in one launch pair (qr_mi_montecarlo_device).
 
-Out of scope: ``mutual_information_base_scheme(_arg)`` and ``mutual_information_X_Y(_int_arg)``, the
-``scipy.integrate.quad`` drivers of the module.
+``mutual_information_base_scheme`` (:123-148) and ``mutual_information_X_Y`` (:202-208) are
+``scipy.integrate.quad`` over ``mutual_information_base_scheme_arg`` (:43-119) and
+``mutual_information_X_Y_int_arg`` (:175-199).  Here the integrands run on the GPU and quad's integrator
+(QUADPACK's QAGS / QAGI, restated operation by operation) on the host around them
+(qr_mi_quad_batch): the floats returned are the reference's, the integrals it returns as ``-inf``
+included.  ``mutual_information_quad_batch`` integrates many mappers / sign configurations in one call,
+one launch per round of bisections; the ``_arg_array`` forms evaluate an integrand over an array.
 """
 from __future__ import annotations
 
@@ -25,7 +30,12 @@ from . import _lib
 from ._lib import check, check_tensor, ptr
 
 __all__ = ["P_xhat", "mutual_information_X_Xhat", "montecarlo_information", "montecarlo_information_device",
-           "which_mask"]
+           "which_mask", "mutual_information_base_scheme_arg", "mutual_information_base_scheme_arg_array",
+           "mutual_information_X_Y_int_arg", "mutual_information_X_Y_int_arg_array", "mutual_information_base_scheme",
+           "mutual_information_X_Y", "mutual_information_quad_batch", "quad_batch_stats", "quad_host", "quad_rule"]
+
+GRID_DEFAULTS = (1e-21, 1000)   # NoiseMapper's trunkation_threshold, n_intervals_per_step (noisemapper.pyx:103-105)
+QUAD_KINDS = {"base": 0, "X_Y": 1}
 
 
 def P_xhat(nm):
@@ -146,3 +156,190 @@ def montecarlo_information_device(nm, p_Xhat, x_fi, y_fi, B, which=np.ones(3, dt
     if stream != current:   # the buffer came from the current stream's pool: keep it until `stream` is done with it
         t.record_stream(stream)
     return (info[:, :B], t) if want_terms else info[:, :B]
+
+
+# ------------------------------------------------------------------ quad-integrated evaluators
+def _kind(kind) -> int:
+    if kind in QUAD_KINDS:
+        return QUAD_KINDS[kind]
+    if kind in (0, 1) and not isinstance(kind, bool):
+        return int(kind)
+    raise ValueError(f"kind must be 'base' or 'X_Y' (0 or 1), got {kind!r}")
+
+
+def _check_limit(limit) -> int:
+    if int(limit) < 1:
+        raise ValueError(f"limit must be at least 1, got {limit}")
+    return int(limit)
+
+
+def _check_pX(p_Xhat, M, what="p_Xhat"):
+    pX = np.ascontiguousarray(np.asarray(p_Xhat, np.float64).ravel())
+    if pX.size != M:
+        raise ValueError(f"{what} has {pX.size} entries, the alphabet {M}")
+    return pX
+
+
+QUAD_MESSAGES = {
+    1: "The maximum number of subdivisions has been achieved.",
+    2: "The occurrence of roundoff error is detected, which prevents the requested tolerance from being achieved.",
+    3: "Extremely bad integrand behavior occurs at some points of the integration interval.",
+    4: "The algorithm does not converge.  Roundoff error is detected in the extrapolation table.",
+    5: "The integral is probably divergent, or slowly convergent.",
+    6: "The input is invalid.",
+}
+
+
+def _warn(ier, abserr):
+    """quad warns whenever QUADPACK's ier is not 0 (the reference does not silence it)."""
+    if not ier:
+        return
+    import warnings
+
+    try:
+        from scipy.integrate import IntegrationWarning as category
+    except Exception:
+        category = UserWarning   # IntegrationWarning's base class
+    warnings.warn(f"{QUAD_MESSAGES.get(int(ier), 'quad: ier = %d' % ier)}  The error may be underestimated "
+                  f"(estimate {abserr!r}).", category, stacklevel=3)
+
+
+def mutual_information_base_scheme_arg_array(n, nm, p_Xhat):
+    """mutual_information_base_scheme_arg (:43-119) at every n: one launch (qr_mi_integrand_host)."""
+    pX = _check_pX(p_Xhat, int(nm.order))
+    n = np.ascontiguousarray(np.asarray(n, np.float64).ravel())
+    out = np.empty(n.size, np.float64)
+    if n.size:
+        _prepare(nm, pX)
+        check(_lib.load().qr_mi_integrand_host(nm.handle, 0, n.size, ptr(n), ptr(out)), "mutual_information_base_scheme_arg")
+    return out
+
+
+def mutual_information_base_scheme_arg(n, nm, p_Xhat):
+    """mutual_information.pyx:43-119"""
+    return float(mutual_information_base_scheme_arg_array(np.array([float(n)]), nm, p_Xhat)[0])
+
+
+def mutual_information_X_Y_int_arg_array(y, nm):
+    """mutual_information_X_Y_int_arg (:175-199) at every y: one launch (qr_mi_integrand_host)."""
+    y = np.ascontiguousarray(np.asarray(y, np.float64).ravel())
+    out = np.empty(y.size, np.float64)
+    if y.size:
+        nm._device_grid()
+        check(_lib.load().qr_mi_integrand_host(nm.handle, 1, y.size, ptr(y), ptr(out)), "mutual_information_X_Y_int_arg")
+    return out
+
+
+def mutual_information_X_Y_int_arg(y, nm):
+    """mutual_information.pyx:175-199"""
+    return float(mutual_information_X_Y_int_arg_array(np.array([float(y)]), nm)[0])
+
+
+def mutual_information_quad_batch(kind, nms, p_Xhats=None, sign_configs=None, *, epsabs=1.49e-8, epsrel=1.49e-8,
+                                  limit=50, stream=None):
+    """P integrals in one call: kind 'base' (mutual_information_base_scheme of nms[k], p_Xhats[k]) or 'X_Y'
+    (mutual_information_X_Y of nms[k]); sign_configs [P][M] uint8, if given, replaces each mapper's own
+    configuration (one NoiseMapper per noise variance then serves every configuration; a mapper may appear
+    many times).  All mappers share one bit_per_symbol.  -> (I [P], abserr [P], neval [P], ier [P]); ier is
+    QUADPACK's, non-zero where scipy's quad would warn.  No warning is raised here."""
+    k = _kind(kind)
+    limit = _check_limit(limit)
+    nms = list(nms)
+    P = len(nms)
+    I, abserr = np.empty(P, np.float64), np.empty(P, np.float64)
+    neval, ier = np.empty(P, np.int32), np.empty(P, np.int32)
+    if P == 0:
+        return I, abserr, neval, ier
+    bps = int(nms[0].bit_per_symbol)
+    M = 1 << bps
+    for q, nm in enumerate(nms):
+        if int(nm.bit_per_symbol) != bps:
+            raise ValueError(f"the mappers of one batch must share bit_per_symbol (mapper {q} has {nm.bit_per_symbol}, "
+                             f"mapper 0 {bps})")
+    pX = None
+    if k == 0:
+        if p_Xhats is None:
+            raise ValueError("the base-scheme integrals need p_Xhats")
+        rows = list(p_Xhats)
+        if len(rows) != P:
+            raise ValueError(f"p_Xhats has {len(rows)} rows for {P} mappers")
+        pX = np.ascontiguousarray(np.stack([_check_pX(r, M, f"p_Xhats[{q}]") for q, r in enumerate(rows)]))
+    cfg = None
+    if sign_configs is not None:
+        cfg = np.asarray(sign_configs)
+        if cfg.dtype == np.bool_:
+            cfg = cfg.view(np.uint8)
+        if cfg.dtype != np.uint8 or cfg.shape != (P, M):
+            raise ValueError(f"sign_configs must be uint8 of shape ({P}, {M}), got {cfg.dtype} {cfg.shape}")
+        cfg = np.ascontiguousarray(cfg)
+    for nm in nms:
+        nm._device_grid()
+    handles = (C.c_void_p * P)(*[nm.handle for nm in nms])
+    check(_lib.load().qr_mi_quad_batch(handles, None if pX is None else ptr(pX), None if cfg is None else ptr(cfg), P, k,
+                                       float(epsabs), float(epsrel), limit, ptr(I), ptr(abserr), ptr(neval), ptr(ier),
+                                       None if stream is None else C.c_void_p(stream.cuda_stream)),
+          "mutual_information_quad_batch")
+    return I, abserr, neval, ier
+
+
+def quad_rule(kind, nm, a, b, p_Xhat=None, sign_config=None):
+    """One work item of the batch's kernel with its debug output (qr_mi_quad_rule_host): the rule of each
+    interval [a[h], b[h]] (one or two).  -> (sums [nh][4] = result, raw error, resabs, resasc;
+    nodes [nh][21 or 30][2] = every lane's abscissa and integrand value).  For tests."""
+    k = _kind(kind)
+    a = np.ascontiguousarray(np.atleast_1d(np.asarray(a, np.float64)))
+    b = np.ascontiguousarray(np.atleast_1d(np.asarray(b, np.float64)))
+    if a.shape != b.shape or a.ndim != 1 or a.size not in (1, 2):
+        raise ValueError("a and b must hold the ends of one or two intervals")
+    M = int(nm.order)
+    pX = None if k == 1 else _check_pX(p_Xhat, M)
+    cfg = None if sign_config is None else np.ascontiguousarray(np.asarray(sign_config, np.uint8).ravel())
+    if cfg is not None and cfg.size != M:
+        raise ValueError(f"sign_config has {cfg.size} entries, the alphabet {M}")
+    nm._device_grid()
+    sums = np.empty((a.size, 4), np.float64)
+    nodes = np.empty((a.size, 30 if k == 1 else 21, 2), np.float64)
+    check(_lib.load().qr_mi_quad_rule_host(nm.handle, None if pX is None else ptr(pX), None if cfg is None else ptr(cfg), k,
+                                           a.size, ptr(a), ptr(b), ptr(sums), ptr(nodes)), "quad_rule")
+    return sums, nodes
+
+
+def quad_batch_stats():
+    """Of this thread's last mutual_information_quad_batch: rounds, launches, work items, and the seconds of
+    host bookkeeping and of the whole call."""
+    out = (C.c_int64 * 5)()
+    check(_lib.load().qr_mi_quad_stats(out), "quad_batch_stats")
+    return {"rounds": int(out[0]), "launches": int(out[1]), "work_items": int(out[2]), "host_s": out[3] * 1e-9,
+            "total_s": out[4] * 1e-9}
+
+
+def mutual_information_base_scheme(nm, p_Xhat, *, epsabs=1.49e-8, epsrel=1.49e-8, limit=50):
+    """mutual_information.pyx:123-148: quad(mutual_information_base_scheme_arg, 0, 1, args=(nm, p_Xhat))[0]; the
+    keywords are quad's, at quad's defaults."""
+    _check_limit(limit)
+    pX = _check_pX(p_Xhat, int(nm.order))
+    I, abserr, _, ier = mutual_information_quad_batch(0, [nm], [pX], epsabs=epsabs, epsrel=epsrel, limit=limit)
+    _warn(int(ier[0]), float(abserr[0]))
+    return float(I[0])
+
+
+def mutual_information_X_Y(nm, *, epsabs=1.49e-8, epsrel=1.49e-8, limit=50):
+    """mutual_information.pyx:202-208: quad(mutual_information_X_Y_int_arg, -inf, inf, args=(nm,))[0]."""
+    _check_limit(limit)
+    I, abserr, _, ier = mutual_information_quad_batch(1, [nm], epsabs=epsabs, epsrel=epsrel, limit=limit)
+    _warn(int(ier[0]), float(abserr[0]))
+    return float(I[0])
+
+
+def quad_host(f, kind, a, b, *, epsabs=1.49e-8, epsrel=1.49e-8, limit=50):
+    """The host integrator alone over a Python callable (qr_quad_host, no device call): kind 0 / 'base' is
+    quad(f, a, b), kind 1 / 'X_Y' quad(f, -inf, inf).  -> (I, abserr, neval, ier, last).  For tests."""
+    k = _kind(kind)
+    limit = _check_limit(limit)
+    L = _lib.load()
+    cb = _lib.QUAD_FN(lambda x, _user: float(f(x)))
+    I, abserr = C.c_double(0), C.c_double(0)
+    neval, ier, last = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(L.qr_quad_host(cb, None, k, float(a), float(b), float(epsabs), float(epsrel), limit, C.byref(I), C.byref(abserr),
+                         C.byref(neval), C.byref(ier), C.byref(last)), "quad_host")
+    return I.value, abserr.value, neval.value, ier.value, last.value

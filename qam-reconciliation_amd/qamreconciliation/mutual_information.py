@@ -1,7 +1,9 @@
 """qamreconciliation.mutual_information (mutual_information.pyx): the names the reference's
-sims/sim_montecarlo_information.py imports, plus the closed-form I(X;Xhat).  The quad-integrated
-evaluators (mutual_information_base_scheme, mutual_information_X_Y and their integrands) are out
-of scope of the MI355X build."""
-from qamr.mutual_information import P_xhat, montecarlo_information, mutual_information_X_Xhat  # noqa: F401
+sims/sim_montecarlo_information.py, sims/sim_mutual_information_base_scheme.py and
+sims/sim_mutual_information_compare_signs.py import, plus the two integrands."""
+from qamr.mutual_information import (P_xhat, montecarlo_information, mutual_information_base_scheme,  # noqa: F401
+                                     mutual_information_base_scheme_arg, mutual_information_X_Xhat,
+                                     mutual_information_X_Y, mutual_information_X_Y_int_arg)
 
-__all__ = ["P_xhat", "montecarlo_information", "mutual_information_X_Xhat"]
+__all__ = ["P_xhat", "montecarlo_information", "mutual_information_X_Xhat", "mutual_information_base_scheme",
+           "mutual_information_base_scheme_arg", "mutual_information_X_Y", "mutual_information_X_Y_int_arg"]
