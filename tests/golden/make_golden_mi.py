@@ -7,7 +7,9 @@ Run where the reference build is available, as tests/golden/make_golden_interp.p
     make -C oracle ref
     PYTHONPATH=oracle/_ref python3 tests/golden/make_golden_mi.py
 
-The reference build (oracle/Makefile `ref`) does not compile mutual_information.pyx, so every value
+When this file was written the reference build (oracle/Makefile `ref`) did not compile
+mutual_information.pyx (it does now: make_golden_wide_interp_mi.retro_check asserts that the compiled
+montecarlo_information returns the totals stored here, bit for bit, for all 8 x 70 blocks), so every value
 the module takes from its NoiseMapper and PAMAlphabet is taken from the compiled reference here too --
 random_symbols, index_to_value, hard_decide_index, map_noise, g_inv, g_inv_search,
 fwrd_transition_probability, delta_F_Y, probabilities, constellation, noise_var, noise_sigma -- and

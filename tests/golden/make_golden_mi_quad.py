@@ -8,7 +8,9 @@ Run where the reference build is available, as tests/golden/make_golden_mi.py:
     make -C oracle ref
     PYTHONPATH=oracle/_ref python3 tests/golden/make_golden_mi_quad.py
 
-The reference build (oracle/Makefile `ref`) does not compile mutual_information.pyx, so every value the
+When this file was written the reference build (oracle/Makefile `ref`) did not compile mutual_information.pyx
+(it does now: make_golden_wide_interp_mi.retro_check asserts that the compiled mutual_information_base_scheme /
+mutual_information_X_Y return the 18 integrals of cases 1..9 stored here, bit for bit), so every value the
 module takes from its NoiseMapper and PAMAlphabet is taken from the compiled reference here too -- g_inv,
 delta_F_Y, probabilities, constellation, noise_var, noise_sigma, and fwrd_transition_probability for
 P_xhat -- and only the two integrands (:43-119, :175-199) are restated below, in plain Python floats
