@@ -30,6 +30,7 @@
 #include <atomic>
 #include <functional>
 
+#include "debug_check.hpp"
 #include "glibc_math.hpp"
 #include "qamr_internal.hpp"
 #include "strict_pack.hpp"
@@ -39,32 +40,6 @@ namespace qr {
 
 enum CheckMode { kFirst = 0, kNormal = 1, kParityOnly = 2 };
 
-// Device-side index checks of the debug build (make -C csrc DEBUG=1 -> qamr/libqamr_debug.so,
-// QR_DEBUG_ASSERT=1; SURVEY.md 5 -- the reference turns bounds checks off, decoder.pyx:181,240,
-// 289,332,399,411): QR_DCHECK(ok, site, a, b) counts every failed check in g_dbg and keeps the
-// first failure's site and two values; the first failing lane also prints them.  Non-fatal (no
-// trap): the test reads the counts through qr_debug_asserts (tests/test_gpu_debug_build.py).  The
-// product library compiles every check away.
-#ifndef QR_DEBUG_ASSERT
-#define QR_DEBUG_ASSERT 0
-#endif
-#if QR_DEBUG_ASSERT
-__device__ unsigned long long g_dbg[4];  // {failed checks, first site, first a, first b}
-__device__ __noinline__ void dcheck_fail(int site, long long a, long long b) {
-    if (atomicAdd(&g_dbg[0], 1ull) == 0ull) {
-        g_dbg[1] = (unsigned long long)site;
-        g_dbg[2] = (unsigned long long)a;
-        g_dbg[3] = (unsigned long long)b;
-        printf("qamr debug check %d failed: a=%lld b=%lld (block %u thread %u)\n", site, a, b, blockIdx.x, threadIdx.x);
-    }
-}
-#define QR_DCHECK(ok, site, a, b)                                   \
-    do {                                                            \
-        if (!(ok)) dcheck_fail((site), (long long)(a), (long long)(b)); \
-    } while (0)
-#else
-#define QR_DCHECK(ok, site, a, b) ((void)0)
-#endif
 // check sites (qr_debug_asserts reports the first failure's site)
 enum DebugSite {
     kDbgLaneFrame = 1,     // lane_frame: a listed column outside the sweep's range
@@ -76,7 +51,7 @@ enum DebugSite {
     kDbgCompact = 7,       // k_compact: list index outside the range
     kDbgResPost = 8,       // k_resident: posterior index outside [0, V)
     kDbgResMsg = 9,        // k_resident: LDS message index outside [0, C D)
-    // 10, 11: the interpolation grid's index checks (demap.hip, GridDebugSite)
+    // 10, 11: the interpolation grid's (grid_interp.hpp GridDebugSite); 12..16: mi.hip (MiDebugSite)
 };
 
 // Check-node arithmetic: the reference's box-plus bit for bit -- glibc exp/log restated
@@ -2275,20 +2250,21 @@ int qr_code_create(const int64_t *e_to_v, const int64_t *e_to_c, int64_t nv, int
 int qr_code_destroy(qr_code *code) { return free_code(code); }
 
 #if QR_DEBUG_ASSERT
-// Debug build only (libqamr_debug.so; not in include/qamr.h): out = {failed device checks, first
-// failing site (DebugSite), its two values}; reads and clears them.
+// Debug build only (libqamr_debug.so; not in include/qamr.h): out = {failed device checks of every
+// unit, first failing site, its two values} -- the first unit with a failure in the order decoder.hip
+// (DebugSite), demap_interp.hip, mi.hip; reads and clears every unit's counter.
 QR_API int qr_debug_asserts(int64_t *out) {
-    unsigned long long h[4] = {0, 0, 0, 0};
+    unsigned long long u[3][4] = {};
     if (hipDeviceSynchronize() != hipSuccess) return QR_EDEVICE;
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(qr::g_dbg), sizeof(h)) != hipSuccess) return QR_EDEVICE;
-    const unsigned long long z[4] = {0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(qr::g_dbg), z, sizeof(z)) != hipSuccess) return QR_EDEVICE;
-    unsigned long long d[4] = {0, 0, 0, 0};   // the interpolation grid's checks (demap.hip)
-    if (int rc = qr::debug_asserts_demap(d)) return rc;
-    if (h[0] == 0)
-        for (int i = 1; i < 4; ++i) h[i] = d[i];
-    h[0] += d[0];
-    for (int i = 0; i < 4; ++i) out[i] = (int64_t)h[i];
+    if (!qr::debug_read_clear(u[0])) return QR_EDEVICE;
+    if (int rc = qr::debug_asserts_interp(u[1])) return rc;
+    if (int rc = qr::debug_asserts_mi(u[2])) return rc;
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    for (int k = 2; k >= 0; --k) {
+        out[0] += (int64_t)u[k][0];
+        if (u[k][0])
+            for (int i = 1; i < 4; ++i) out[i] = (int64_t)u[k][i];
+    }
     return QR_OK;
 }
 #endif

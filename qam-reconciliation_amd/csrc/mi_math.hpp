@@ -1,6 +1,6 @@
 // mi_math.hpp -- per-sample arithmetic of the Monte-Carlo mutual-information estimator
 // (mutual_information.pyx:218-297, montecarlo_information), written once: the gfx950 kernel
-// (demap.hip k_mi_terms) and the host check (tests/native/mi_check.cpp) both call
+// (mi.hip k_mi_terms) and the host check (tests/native/mi_check.cpp) both call
 // mi_sample_terms below, with their own providers of y_hat, exp and log2.  The integrands of the
 // quad-integrated evaluators (:43-119, :175-199) and the Gauss-Kronrod rules follow further down.
 //
@@ -83,7 +83,7 @@ QR_HD void mi_sample_terms(const DemapTables &t, const double *pX, const double 
 
 // ---------------------------------------------------------------------------------------------
 // The quad-integrated evaluators (mutual_information.pyx:43-119 and :175-199): the two integrands,
-// written once for the gfx950 kernel (demap.hip k_mi_quad / k_mi_integrand) and the host check
+// written once for the gfx950 kernel (mi.hip k_mi_quad / k_mi_integrand) and the host check
 // (tests/native/mi_quad_check.cpp), and the two Gauss-Kronrod rules QUADPACK applies to them
 // (dqk21 on [0, 1], dqk15i on (-inf, inf)), split into "abscissa of node k" (one lane each) and "the
 // rule's four sums in the rule's order" (one lane per interval).  Every operation is rounded on its

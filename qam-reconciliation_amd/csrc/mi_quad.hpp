@@ -10,7 +10,7 @@
 // names the interval(s) to evaluate next, QuadState::feed takes their {result, abserr, resabs,
 // resasc} (after quad_rule_tail) and advances by one bisection: the round-off tests, dqpsrt, the
 // extrapolation bookkeeping and dqelg, then termination.  It ends after at most `limit` feeds.  The
-// batched GPU driver (demap.hip qr_mi_quad_batch) runs one state per integral and evaluates the
+// batched GPU driver (mi.hip qr_mi_quad_batch) runs one state per integral and evaluates the
 // pending intervals of all unfinished ones in one launch per round; qr_quad_host runs one state over a
 // C callback.  Both are synchronous (a round's launch depends on the host's decisions of the round
 // before), so neither can be captured into a graph.  The per-integral bookkeeping is O(limit) per

@@ -92,18 +92,27 @@ int launch_transpose_to_fi_i64(int B, int ld, int64_t n, const int64_t *src, int
 
 extern std::atomic<int> g_demap_fast;  // demap.hip (tuning knob "demap_fast")
 extern std::atomic<int> g_demap_hyp;   // demap.hip (tuning knob "demap_hyp")
-extern std::atomic<int> g_interp_fast; // demap.hip (tuning knob "interp_fast")
-extern std::atomic<int> g_interp_seg;  // demap.hip (tuning knob "interp_seg")
+extern std::atomic<int> g_interp_fast; // demap_interp.hip (tuning knob "interp_fast")
+extern std::atomic<int> g_interp_seg;  // demap_interp.hip (tuning knob "interp_seg")
 
-// Debug build (libqamr_debug.so, QR_DEBUG_ASSERT=1): device-side index checks.  decoder.hip and
-// demap.hip each count their own failed checks; qr_debug_asserts (decoder.hip) reports both.
+// Host helpers shared by demap.hip, demap_interp.hip and mi.hip.
+int check_shape(int B, int ld, int64_t S);                // demap.hip: 0 < B <= ld, ld % 64 == 0, S > 0
+unsigned demap_wave_grid(int device, int64_t items);      // demap.hip: workgroups of a grid-stride launch
+struct GridView;                                          // grid_interp.hpp
+GridView grid_view(const qr_demap *dm);                   // demap_interp.hip: the handle's grid, as the kernels take it
+bool grid_fast(const qr_demap *dm);                       // demap_interp.hip: body (b) of the grid's index search
+int need_grid(const qr_demap *dm);                        // demap_interp.hip: an error unless the grid was created
+
+// Debug build (libqamr_debug.so, QR_DEBUG_ASSERT=1): device-side index checks (debug_check.hpp).
+// Every unit that carries checks counts its own failures and exports one reader: h = {failed
+// checks, first site, first a, first b}, read and cleared; qr_debug_asserts (decoder.hip) reports
+// their sum and the first failing site in the order decoder.hip, demap_interp.hip, mi.hip.
 #ifndef QR_DEBUG_ASSERT
 #define QR_DEBUG_ASSERT 0
 #endif
 #if QR_DEBUG_ASSERT
-// demap.hip: h = {failed checks, first site, first a, first b} of the interpolation grid's index
-// checks; reads and clears them.
-int debug_asserts_demap(unsigned long long h[4]);
+int debug_asserts_interp(unsigned long long h[4]);   // demap_interp.hip
+int debug_asserts_mi(unsigned long long h[4]);       // mi.hip
 #endif
 
 struct DeviceGuard {

@@ -7,8 +7,8 @@
 //                                   integrator-only records: result and abserr bit-equal to scipy's,
 //                                   neval equal, (ier != 0) == warned
 //   mi_quad_check case FILE         mi_base_arg / mi_xy_arg (the functions the kernel calls) at the
-//                                   fixture's abscissae with host providers -- y_hat by a host g_inv on a
-//                                   host-built grid, the restated glibc exp / log2 -- bit-equal to the
+//                                   fixture's abscissae with host providers -- y_hat by grid_interp.hpp's g_inv
+//                                   (the kernels' own) on a host-built grid, the restated glibc exp / log2 -- bit-equal to the
 //                                   fixture's values; with the header's flag set, also both integrals
 //                                   wholly on the host through the same driver, bit-equal
 #include <cmath>
@@ -22,6 +22,7 @@
 #include "glibc_math.hpp"
 #include "qamr_math.hpp"
 #include "host_build.hpp"
+#include "grid_interp.hpp"
 #include "mi_math.hpp"
 #include "mi_quad.hpp"
 
@@ -115,40 +116,17 @@ static int check_integrator(const char *path) {
     return bad ? 1 : 0;
 }
 
-// NoiseMapper.g_inv on the host: the grid of noisemapper.pyx:135-144 as qr_demap_grid_create builds it,
-// __interp / __binsearch of :27-63 (binsearch_thr is that search over a plain array).
-struct HostGrid {
-    std::vector<double> F, y;
-    void build(const qr::DemapTables &t, double trunc, double nips, double step) {
-        const double sigma = sqrt(t.two_s2 / 2);
-        double y_low, y_high;
-        if (trunc > 1.) {
-            y_low = t.a[0] * 10;
-            y_high = t.a[t.M - 1] * 10;
-        } else {
-            const double tmp = sqrt(-2. * log(trunc)) * sigma;
-            y_high = t.a[t.M - 1] + tmp;
-            y_low = t.a[0] - tmp;
-        }
-        const int n = (int)(ceil((y_high - y_low) * nips / step) + 1);
-        const double lin_step = (y_high - y_low) / (double)(n - 1);
-        F.resize((size_t)n);
-        y.resize((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            y[(size_t)i] = (i == n - 1) ? y_high : (double)i * lin_step + y_low;
-            F[(size_t)i] = qr::public_F_Y(t, y[(size_t)i]);
-        }
+// The grid of noisemapper.pyx:135-144 on the host, as qr_demap_grid_create builds it (grid_interp.hpp).
+static std::vector<double2> build_grid(const qr::DemapTables &t, double trunc, double nips, double step) {
+    const qr::GridGeometry geo = qr::grid_geometry(t, trunc, nips, step);
+    const int n = (int)geo.n_points;
+    std::vector<double2> pairs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        pairs[(size_t)i].y = qr::grid_point(geo.y_low, geo.y_high, geo.lin_step, n, i);
+        pairs[(size_t)i].x = qr::public_F_Y(t, pairs[(size_t)i].y);
     }
-    double g_inv(const qr::DemapTables &t, double n_hat, int i) const {
-        const double val = qr::search_target(t, n_hat, i);
-        const int n = (int)F.size();
-        if (val >= F[(size_t)n - 1]) return y[(size_t)n - 1];
-        const int r = qr::binsearch_thr(F.data(), n, val);
-        if (r == n - 1) return y[(size_t)n - 1];
-        if (F[(size_t)r + 1] == F[(size_t)r]) return y[(size_t)r];
-        return y[(size_t)r] + (y[(size_t)r + 1] - y[(size_t)r]) * (val - F[(size_t)r]) / (F[(size_t)r + 1] - F[(size_t)r]);
-    }
-};
+    return pairs;
+}
 
 static int check_case(const char *path) {
     Reader in(path);
@@ -168,8 +146,8 @@ static int check_case(const char *path) {
         printf("FAIL build_demap_host: %s\n", err.c_str());
         return 1;
     }
-    HostGrid grid;
-    grid.build(t, hd[3], hd[4], hd[5]);
+    const std::vector<double2> pairs = build_grid(t, hd[3], hd[4], hd[5]);
+    const qr::GridView grid{pairs.data(), nullptr, (int)pairs.size(), 0, 0, pairs.back().x, pairs.back().y};   // body (a): no coarse table
     qr::GlibcTables GT;
     qr::build_glibc_tables(&GT);
     static const qr::GlibcLog2 L2 = QR_GLIBC_LOG2_INIT;
@@ -177,7 +155,7 @@ static int check_case(const char *path) {
     auto lg = [&](double v) { return qr::g_log2_full(v, L2); };
     auto base = [&](double n) {
         double yh[64];
-        for (int i = 0; i < M; ++i) yh[i] = grid.g_inv(t, n, i);
+        for (int i = 0; i < M; ++i) yh[i] = qr::grid_g_inv<false>(t, grid, nullptr, n, i);
         return qr::mi_base_arg(t, pX, M, [&](int i) { return yh[i]; }, ex, lg);
     };
     auto xy = [&](double y) { return qr::mi_xy_arg(t, M, y, ex, lg); };

@@ -403,7 +403,7 @@ PARITY = ([f"test_grid_matches_reference[{c}]" for c in DEBUG_CASES] +
 
 def test_debug_build_interp_index_checks(gpu):
     """This file's parity tests in a child process on libqamr_debug.so: the grid index checks
-    (0 <= r, r + 1 < n_points where pair r + 1 is read, the coarse-table index; demap.hip QR_DCHECK)
+    (0 <= r, r + 1 < n_points where pair r + 1 is read, the coarse-table index; grid_interp.hpp QR_DCHECK)
     never fail -- conftest's autouse fixture fails any test after which one did."""
     assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
     env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")

@@ -314,7 +314,7 @@ PARITY = ([f"test_device_blocks_vs_reference[{c}]" for c in CASES] + ["test_whic
 
 def test_debug_build_mi_index_checks(gpu):
     """This file's parity tests in a child process on libqamr_debug.so: the symbol, decision and grid
-    index checks of k_mi_terms (demap.hip QR_DCHECK) never fail -- conftest's autouse fixture fails any
+    index checks of k_mi_terms (mi.hip QR_DCHECK) never fail -- conftest's autouse fixture fails any
     test after which one did."""
     assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
     env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")

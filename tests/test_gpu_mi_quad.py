@@ -261,8 +261,8 @@ PARITY = ([f"test_integrands_vs_reference[{c}]" for c in CASES] + [f"test_integr
 
 def test_debug_build_quad_index_checks(gpu):
     """This file's parity tests in a child process on libqamr_debug.so: the node, LDS-slot, problem-id and grid
-    index checks of k_mi_quad / k_mi_integrand (demap.hip QR_DCHECK) never fail -- conftest's autouse fixture
-    fails any test after which one did."""
+    index checks of k_mi_quad / k_mi_integrand (mi.hip, grid_interp.hpp QR_DCHECK) never fail -- conftest's autouse
+    fixture fails any test after which one did."""
     assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
     env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",

@@ -329,7 +329,7 @@ PARITY = ([f"test_grid_and_tables_match_reference[{k}]" for k in DEBUG_CASES] +
 
 def test_debug_build_wide_index_checks(gpu):
     """This file's parity tests for cases 2, 3, 4 and 7 in a child process on libqamr_debug.so: the grid, coarse
-    table, symbol, decision, node, LDS-slot and problem-id index checks (demap.hip QR_DCHECK) never fail --
+    table, symbol, decision, node, LDS-slot and problem-id index checks (grid_interp.hpp, mi.hip QR_DCHECK) never fail --
     conftest's autouse fixture fails any test after which one did."""
     assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
     env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")

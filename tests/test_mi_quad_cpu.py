@@ -1,7 +1,7 @@
 """CPU-side checks of the quad-integrated mutual-information evaluators: the fixture
 (tests/golden/mi_quad.npz, written by tests/golden/make_golden_mi_quad.py), the host integrator and the
 two integrands' arithmetic (tests/native/mi_quad_check.cpp runs the very functions the kernel and the
-batched driver run), qr_quad_host through ctypes, the argument checks, the CLIs' parsers and
+batched driver run, the interpolated g_inv of csrc/grid_interp.hpp included), qr_quad_host through ctypes, the argument checks, the CLIs' parsers and
 configuration lists, and the reference's import lines."""
 import ctypes as C
 import math
