@@ -352,6 +352,31 @@ QR_API int qr_count_errors_device(int32_t B, int32_t ld, int64_t K, const double
                            const uint8_t *d_success, const int32_t *d_iters, int32_t *d_frame_errors,
                            int64_t *d_counters, void *stream);
 
+/* ------------------------------------ code evaluation on a binary channel */
+/* The decoder's input of sims/sim_decode.py and sims/sim_direct.py, frame-innermost:
+ * d_word[V][ld] (bits), d_z[V][ld] (standard normal draws) -> d_llr[V][ld], columns [0, B) only.
+ *   hard == 0 (sim_decode.py:98-100): coef * ((1 - 2 w) + vsqrt * z), coef = 2 alpha / v;
+ *   hard != 0 (:69-71): coef * sign((1 - 2 w) + vsqrt * z), coef = LLR0, sign as numpy.sign
+ *     (-1, 0, +1, NaN for NaN, +0.0 for -0.0).
+ * Every operation is rounded on its own and the last one is a multiply, so coef = inf against a
+ * zero gives NaN as in the reference.  One launch on `stream`, asynchronous, allocates nothing,
+ * capturable.  QR_EVALUE: a null pointer, B < 1, B > ld, ld % 64 != 0, V < 1. */
+QR_API int qr_biawgn_llr_device(int32_t hard, double coef, double vsqrt, int32_t B, int32_t ld, int64_t V,
+                                const uint8_t *d_word, const double *d_z, double *d_llr, void *stream);
+/* The decoder's input of sims/sim_bsc.py:58-61: d_llr = coef * (1 - 2 (w ^ (u < rber))) with
+ * d_u[V][ld] uniform draws in [0, 1) and coef = log2(1 - rber) - log2(rber); d_rx_or_null[V][ld],
+ * when given, receives the channel's output bits w ^ (u < rber).  Same layout, checks and launch
+ * properties as qr_biawgn_llr_device. */
+QR_API int qr_bsc_llr_device(double coef, double rber, int32_t B, int32_t ld, int64_t V, const uint8_t *d_word,
+                             const double *d_u, double *d_llr, uint8_t *d_rx_or_null, void *stream);
+/* qr_count_errors_device with the decision rule of sim_decode.py:80 and sim_bsc.py:66: a bit is 1
+ * iff its final LAPPR is < 0, so a NaN decides 0 (count_errors_from_lappr decides 1 for it).  Same
+ * arguments, outputs and counters; K = V counts every bit (the BSC script).  QR_EVALUE for a null
+ * pointer as well. */
+QR_API int qr_count_errors_neg_device(int32_t B, int32_t ld, int64_t K, const double *d_final, const uint8_t *d_word,
+                                      const uint8_t *d_success, const int32_t *d_iters, int32_t *d_frame_errors,
+                                      int64_t *d_counters, void *stream);
+
 /* --------------------------------------------------------- layout helpers */
 /* Frame-major [B][n] <-> frame-innermost [n][ld] transposes on the device. */
 QR_API int qr_to_frame_innermost_f64(int32_t B, int32_t ld, int64_t n, const double *d_src, double *d_dst, void *stream);

@@ -319,7 +319,9 @@ __global__ void __launch_bounds__(256) k_syndrome(int64_t C, int ld, int B, cons
 }
 
 // utils.pyx:27-40 (lappr >= 0 decides bit 0) over the first K nodes, then the
-// per-frame bookkeeping of reconciliation.pyx:149-157.
+// per-frame bookkeeping of reconciliation.pyx:149-157.  kNeg: the rule of sims/sim_decode.py:80
+// and sims/sim_bsc.py:66 instead, lappr < 0 decides bit 1 (the two differ on a NaN only).
+template <bool kNeg>
 __global__ void __launch_bounds__(256) k_count_errors(int B, int ld, int64_t K, int64_t kpb,
                                                       const double *__restrict__ fin,
                                                       const uint8_t *__restrict__ word, int32_t *__restrict__ ferr) {
@@ -330,7 +332,9 @@ __global__ void __launch_bounds__(256) k_count_errors(int B, int ld, int64_t K, 
     int32_t cnt = 0;
     for (int64_t v = v0; v < v1; ++v) {
         const uint8_t w = word[v * ld + f];
-        cnt += (fin[v * ld + f] >= 0) ? w : 1 - w;
+        const double x = fin[v * ld + f];
+        const bool zero = kNeg ? !(x < 0) : (x >= 0);
+        cnt += zero ? w : 1 - w;
     }
     if (cnt) atomicAdd(&ferr[f], cnt);
 }
@@ -361,6 +365,28 @@ __global__ void k_count_finish(int B, const int32_t *__restrict__ ferr, const ui
         atomicAdd(&counters[3], it);
         atomicAdd(&counters[4], fr);
     }
+}
+
+// qr_count_errors_device (neg = false) and qr_count_errors_neg_device (binary_channel.hip).
+int launch_count_errors(bool neg, int B, int ld, int64_t K, const double *d_final, const uint8_t *d_word,
+                        const uint8_t *d_success, const int32_t *d_iters, int32_t *ferr, int64_t *d_counters,
+                        hipStream_t s) {
+    int rc = check_shape(B, ld, 1);
+    if (rc) return rc;
+    if (K < 0) return set_error(QR_EVALUE, "K must be >= 0");
+    ProfScope ps(neg ? "count_neg" : "count", s);
+    QR_HIP(hipMemsetAsync(ferr, 0, (size_t)B * 4, s));
+    if (K > 0) {
+        const int ft = frame_tile(ld);
+        const int64_t kpb = 64;
+        dim3 grid((unsigned)((K + kpb - 1) / kpb), (unsigned)(ld / ft));
+        if (neg) k_count_errors<true><<<grid, ft, 0, s>>>(B, ld, K, kpb, d_final, d_word, ferr);
+        else k_count_errors<false><<<grid, ft, 0, s>>>(B, ld, K, kpb, d_final, d_word, ferr);
+        QR_LAUNCH_CHECK();
+    }
+    k_count_finish<<<(B + 255) / 256, 256, 0, s>>>(B, ferr, d_success, d_iters, (unsigned long long *)d_counters);
+    QR_LAUNCH_CHECK();
+    return QR_OK;
 }
 
 int check_shape(int B, int ld, int64_t S) {
@@ -630,23 +656,8 @@ int qr_syndrome_device(const qr_code *code, int32_t B, int32_t ld, const uint8_t
 int qr_count_errors_device(int32_t B, int32_t ld, int64_t K, const double *d_final, const uint8_t *d_word,
                            const uint8_t *d_success, const int32_t *d_iters, int32_t *d_frame_errors,
                            int64_t *d_counters, void *stream) {
-    int rc = check_shape(B, ld, 1);
-    if (rc) return rc;
-    if (K < 0) return set_error(QR_EVALUE, "K must be >= 0");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("count", s);
-    int32_t *ferr = d_frame_errors;
-    QR_HIP(hipMemsetAsync(ferr, 0, (size_t)B * 4, s));
-    if (K > 0) {
-        const int ft = frame_tile(ld);
-        const int64_t kpb = 64;
-        dim3 grid((unsigned)((K + kpb - 1) / kpb), (unsigned)(ld / ft));
-        k_count_errors<<<grid, ft, 0, s>>>(B, ld, K, kpb, d_final, d_word, ferr);
-        QR_LAUNCH_CHECK();
-    }
-    k_count_finish<<<(B + 255) / 256, 256, 0, s>>>(B, ferr, d_success, d_iters, (unsigned long long *)d_counters);
-    QR_LAUNCH_CHECK();
-    return QR_OK;
+    return launch_count_errors(false, B, ld, K, d_final, d_word, d_success, d_iters, d_frame_errors, d_counters,
+                               (hipStream_t)stream);
 }
 
 }  // extern "C"

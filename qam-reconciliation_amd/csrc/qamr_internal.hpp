@@ -95,9 +95,13 @@ extern std::atomic<int> g_demap_hyp;   // demap.hip (tuning knob "demap_hyp")
 extern std::atomic<int> g_interp_fast; // demap_interp.hip (tuning knob "interp_fast")
 extern std::atomic<int> g_interp_seg;  // demap_interp.hip (tuning knob "interp_seg")
 
-// Host helpers shared by demap.hip, demap_interp.hip and mi.hip.
+// Host helpers shared by demap.hip, demap_interp.hip, mi.hip and binary_channel.hip.
 int check_shape(int B, int ld, int64_t S);                // demap.hip: 0 < B <= ld, ld % 64 == 0, S > 0
 unsigned demap_wave_grid(int device, int64_t items);      // demap.hip: workgroups of a grid-stride launch
+// demap.hip: the two launches of qr_count_errors_device; neg = the `final < 0` rule of binary_channel.hip
+int launch_count_errors(bool neg, int B, int ld, int64_t K, const double *d_final, const uint8_t *d_word,
+                        const uint8_t *d_success, const int32_t *d_iters, int32_t *ferr, int64_t *d_counters,
+                        hipStream_t s);
 struct GridView;                                          // grid_interp.hpp
 GridView grid_view(const qr_demap *dm);                   // demap_interp.hip: the handle's grid, as the kernels take it
 bool grid_fast(const qr_demap *dm);                       // demap_interp.hip: body (b) of the grid's index search

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -174,40 +175,61 @@ def shard_counters(ferr, succ, its, n: int):
                         torch.tensor(n, dtype=torch.int64, device=ferr.device)])
 
 
+@dataclass(frozen=True)
+class StopRule:
+    """A sequential frame loop's stopping rule, both parts monotone in the frame index: the loop
+    stops after the first 0-based frame w at which the running sum of counter `counter` (0 = bit
+    errors, 1 = frame errors) over frames 0..w is >= `need` and w >= `first_index`.  The rule of
+    reconciliation.pyx:159-161 is StopRule(1, ferr_count_min, floor(simulation_loops / 20) + 1):
+    what run_frames and first_stop_frame apply when no rule is given."""
+    counter: int
+    need: int
+    first_index: int
+
+    def holds(self, counters) -> bool:
+        """After the last frame counted (counters[4] frames)."""
+        return int(counters[self.counter]) >= self.need and int(counters[4]) - 1 >= self.first_index
+
+
 def first_stop_frame(prev_frame_errors: int, ferr, start: int, done: int, ferr_count_min: int,
-                     simulation_loops: int) -> int:
+                     simulation_loops: int, rule: StopRule | None = None) -> int:
     """Global index of the first frame of this batch after which reconciliation.pyx:159-161
     holds: frame_error_count >= ferr_count_min and wordcount > simulation_loops / 20.  Both
     parts are monotone in the frame index, so it is max(first frame where the running frame-error
     count reaches the minimum, first index above loops / 20).  ferr: this rank's per-frame bit
-    errors of its frames [done + start, done + start + len(ferr)); a collective over the ranks."""
+    errors of its frames [done + start, done + start + len(ferr)); a collective over the ranks.
+    With a `rule`, that rule instead: prev_frame_errors is then the rule's counter before this
+    batch, and ferr_count_min and simulation_loops are not read."""
     import torch
 
     world, rank, _ = dist.env_world()
     dev = ferr.device
-    flags = (ferr > 0).to(torch.int64)
+    if rule is None:
+        rule = StopRule(1, ferr_count_min, math.floor(simulation_loops / 20) + 1)
+    flags = (ferr > 0).to(torch.int64) if rule.counter == 1 else ferr.to(torch.int64)
     per_rank = torch.zeros(world, dtype=torch.int64, device=dev)
     per_rank[rank] = flags.sum()
-    dist.all_reduce_sum(per_rank)                               # frame errors of every rank's shard
+    dist.all_reduce_sum(per_rank)                               # the counter's share of every rank's shard
     before = prev_frame_errors + int(per_rank[:rank].sum())     # shards are in rank order
     big = 1 << 62
     g_fe = big
     if flags.numel():
-        hit = torch.nonzero(before + torch.cumsum(flags, 0) >= ferr_count_min)
+        hit = torch.nonzero(before + torch.cumsum(flags, 0) >= rule.need)
         if hit.numel():
             g_fe = done + start + int(hit[0, 0])
     t = torch.tensor([g_fe], dtype=torch.int64, device=dev)
     dist.all_reduce_min(t)
-    g_w = math.floor(simulation_loops / 20) + 1                 # first wordcount > loops / 20
-    return max(int(t.item()), g_w)
+    return max(int(t.item()), rule.first_index)
 
 
-def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int, device=None):
+def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int, device=None,
+               rule: StopRule | None = None):
     """The frame loop of reconciliation.pyx:127-168 over batches of batch * world frames,
     each rank taking its contiguous shard (dist.shard).  frame_fn(batch_index, start, B) ->
     (ferr, succ, its, delta) for this rank's B frames [done + start, done + start + B) of the
     batch (delta = their five counters).  Returns the five global counters at the reference's
-    stopping frame: {bit_errors, frame_errors, successes, iteration_sum, frames = wordcount+1}."""
+    stopping frame: {bit_errors, frame_errors, successes, iteration_sum, frames = wordcount+1}.
+    `rule`: another monotone stopping rule in place of :159-161 (ferr_count_min is then not read)."""
     import torch
 
     world, rank, _ = dist.env_world()
@@ -225,9 +247,10 @@ def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int,
             delta = torch.zeros(5, dtype=torch.int64, device=device)
         dist.all_reduce_sum(delta)
         after = (total + delta).cpu().numpy()
-        if dist.early_stop(after, ferr_count_min, simulation_loops):
+        if dist.early_stop(after, ferr_count_min, simulation_loops) if rule is None else rule.holds(after):
             # the reference stopped at some frame of this batch: cut every counter there
-            g = first_stop_frame(int(total[1]), ferr, start, done, ferr_count_min, simulation_loops)
+            prev = int(total[1 if rule is None else rule.counter])
+            g = first_stop_frame(prev, ferr, start, done, ferr_count_min, simulation_loops, rule)
             keep = min(max(g - (done + start) + 1, 0), B)
             part = shard_counters(ferr, succ, its, keep) if keep else torch.zeros(5, dtype=torch.int64,
                                                                                  device=device)
