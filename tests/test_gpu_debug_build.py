@@ -9,7 +9,11 @@ posterior and message indices (k_resident).  This test runs the repack parity te
 sets, transitions, narrow sweeps; a short max_iterations; the captured decode), the schedule and
 tuning invariance test, and the frame-resident parity tests (configs[1] full batch, ragged batch
 shapes), and the repack on small codes with an unpacked check class (degree 12 as the only class and
-as the side class: tests/test_gpu_repack_small_codes.py, every knob set) in a child process on that library; conftest's autouse fixture fails any test after which a device check failed."""
+as the side class: tests/test_gpu_repack_small_codes.py, every knob set), the frame-resident decode
+of codes past one pass of its 512 threads and with isolated variables, the repack with irregular
+variable degrees (tests/test_gpu_resident_shapes.py) and three entries of the degree matrix
+(tests/test_gpu_degree_matrix.py: narrow sweeps of degrees 8 and 2, unpacked degree 15) in a child
+process on that library; conftest's autouse fixture fails any test after which a device check failed."""
 import os
 import subprocess
 import sys
@@ -33,6 +37,17 @@ CASES = [
     "tests/test_gpu_parity_edges.py::test_resident_batch_shapes_vs_oracle",
     "tests/test_gpu_repack_small_codes.py::test_repack_small_codes_vs_oracle[reg12-clean]",
     "tests/test_gpu_repack_small_codes.py::test_repack_small_codes_vs_oracle[side12-clean]",
+    # the frame-resident decode past one pass of its threads and with isolated variables, the
+    # repack with irregular variable degrees, narrow sweeps of degrees 8 and 2, unpacked degree 15
+    "tests/test_gpu_resident_shapes.py::test_resident_shapes_vs_oracle[v2c3_1536]",
+    "tests/test_gpu_resident_shapes.py::test_resident_shapes_vs_oracle[v2c4_1500]",
+    "tests/test_gpu_resident_shapes.py::test_resident_shapes_vs_oracle[v1c2_2304]",
+    "tests/test_gpu_resident_shapes.py::test_resident_shapes_vs_oracle[v3c9_1152]",
+    "tests/test_gpu_resident_shapes.py::test_resident_shapes_vs_oracle[irr_c6_1100]",
+    "tests/test_gpu_resident_shapes.py::test_irregular_var_repack_vs_oracle[irr6]",
+    "tests/test_gpu_degree_matrix.py::test_degree_matrix_vs_oracle[8-clean]",
+    "tests/test_gpu_degree_matrix.py::test_degree_matrix_vs_oracle[2-special]",
+    "tests/test_gpu_degree_matrix.py::test_degree_matrix_vs_oracle[15-clean]",
 ]
 
 
@@ -43,4 +58,4 @@ def test_debug_build_device_checks(gpu):
                        env=env, capture_output=True, text=True, timeout=900)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
-    assert "14 passed" in r.stdout, tail  # the 11 cases above (the batch-shape test has 4 parameters)
+    assert "23 passed" in r.stdout, tail  # the 20 cases above (the batch-shape test has 4 parameters)
