@@ -65,7 +65,8 @@ QR_API int qr_profile_reset(void);
 QR_API int qr_profile_select(const char *names);
 /* name: "check" (one check sweep, all degree classes), "check_d<D>" (the launch
  * for check degree D), "check1" (first sweep), "var", "var_init", "status",
- * "parity", "demap", "demap_interp", "bob", "syndrome", "count".  Synchronises pending events. */
+ * "parity", "demap", "demap_interp", "bob", "syndrome", "count"; the few-frame schedule:
+ * "few_check" (every check-sweep launch), "few_var", "few_var_init".  Synchronises pending events. */
 QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launches);
 
 /* Kernel-geometry knobs (process-wide; performance only, results unchanged):
@@ -80,7 +81,10 @@ QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launche
  * where the grid is nondecreasing, 0 = the reference's __binsearch probe for probe),
  * "interp_seg" (log2 of the grid entries per coarse-table segment, default 4, used from 1 to 20
  * and raised until the coarse table has at most 4096 entries; read by qr_demap_grid_create, which
- * rebuilds a grid made under another value). */
+ * rebuilds a grid made under another value), "resident" (1 = small single-degree codes decode
+ * frame-resident in LDS, one launch per decode), "few_max" (qr_decode_frames_device and
+ * qr_decode_host decode up to this many frames with the few-frame schedule; 0..64, 0 = off, any
+ * other value is QR_EVALUE and changes nothing). */
 QR_API int qr_tune_set(const char *name, int64_t value);
 QR_API int qr_tune_get(const char *name, int64_t *value);
 
@@ -137,8 +141,25 @@ QR_API int qr_decode_batch_device(const qr_code *code, int32_t B, int32_t ld, co
 QR_API int qr_decode_repack_stats(const qr_code *code, int32_t ld, int32_t max_iterations, const void *d_workspace,
                                   size_t workspace_bytes, int32_t *out);
 
+/* Batched Decoder._decode on FRAME-MAJOR device arrays: d_lappr [B][V], d_synd [B][C] -> d_final [B][V],
+ * d_success [B], d_iters [B].  Any B >= 1.
+ * B <= tuning knob "few_max" frames of a code whose check degrees all lie in 2..16 (and that the
+ * frame-resident decode does not take: see knob "resident") run the few-frame schedule straight on
+ * the caller's arrays: a lane is one check (or one variable) of one frame, one launch per sweep and
+ * degree class, messages frame-major in the workspace.  Anything else is transposed into the
+ * workspace, decoded by qr_decode_batch_device at ld = B rounded up to 64, and transposed back.
+ * Either way the results are those of qr_decode_batch_device, bit for bit.
+ * qr_decode_frames_workspace_size covers both routes, so a knob changed between sizing and decoding
+ * cannot make the workspace short.  Asynchronous on `stream`, no allocation, capturable into a HIP
+ * graph; errors as qr_decode_batch_device. */
+QR_API int qr_decode_frames_workspace_size(const qr_code *code, int32_t B, int32_t max_iterations, size_t *bytes);
+QR_API int qr_decode_frames_device(const qr_code *code, int32_t B, const double *d_lappr, const uint8_t *d_synd,
+                            int32_t max_iterations, double *d_final, uint8_t *d_success, int32_t *d_iters,
+                            void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Decoder.decode (decoder.pyx:441-455) for B frames from host memory,
- * frame-major: lappr[B][V], synd[B][C], final[B][V]. */
+ * frame-major: lappr[B][V], synd[B][C], final[B][V]: host-to-device copies, qr_decode_frames_device
+ * on the handle's scratch, device-to-host copies. */
 QR_API int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, const uint8_t *synd, int32_t max_iterations,
                    double *final_lappr, uint8_t *success, int32_t *iterations);
 

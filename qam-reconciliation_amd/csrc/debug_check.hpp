@@ -8,7 +8,8 @@
 // No relocatable device code, so every translation unit that includes this header carries its own
 // counter; it exports one reader built on debug_read_clear, and qr_debug_asserts (decoder.hip)
 // adds them up.  The site numbers are one list across the units: 1..9 decoder.hip (DebugSite),
-// 10..11 grid_interp.hpp (GridDebugSite), 12..16 mi.hip (MiDebugSite).
+// 10..11 grid_interp.hpp (GridDebugSite), 12..16 mi.hip (MiDebugSite), 17..19 decoder.hip again
+// (the few-frame sweeps: 17 lane -> (class, check), 18 gathered posterior index, 19 message slot).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -27,6 +27,8 @@
 // few, moved to contiguous columns (column repack)); all frames in lock-step
 // (run_flat); small codes with one launch per iteration (run_iter) or one launch
 // per decode with a workgroup per frame and its messages in LDS (k_resident).
+// A few frames on frame-major arrays (decode_frames_device, qr_decode_host): a lane per
+// check / variable of one frame, one launch per sweep (run_few).
 #include <atomic>
 #include <functional>
 
@@ -52,6 +54,9 @@ enum DebugSite {
     kDbgResPost = 8,       // k_resident: posterior index outside [0, V)
     kDbgResMsg = 9,        // k_resident: LDS message index outside [0, C D)
     // 10, 11: the interpolation grid's (grid_interp.hpp GridDebugSite); 12..16: mi.hip (MiDebugSite)
+    kDbgFewCheck = 17,     // few-frame check sweep: lane -> (class, check): check id or its degree
+    kDbgFewPost = 18,      // few-frame check sweep: gathered posterior index outside [0, V)
+    kDbgFewSlot = 19,      // few-frame sweeps: message slot outside [0, E)
 };
 
 // Check-node arithmetic: the reference's box-plus bit for bit -- glibc exp/log restated
@@ -929,6 +934,148 @@ __global__ void __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_e
     else resident_loop<D, false>(a, f, msg, post, tab, wb);
 }
 
+// ---------------------------------------------------------------------------------------
+// Few frames (qr_decode_frames_device with B <= knob few_max; Decoder.decode's one frame): the
+// frame-parallel sweeps give every check a wave of 64 frames, so a single frame keeps 1 lane of
+// 64 busy, and k_resident takes only single-class codes whose messages fit LDS.  Here the
+// arithmetic of k_resident's loop body is cut at its barriers into launches: a lane is one check
+// (k_few_check) or one variable (k_few_var) of the frame blockIdx.y, messages and posteriors
+// live in HBM, frame-major -- posteriors post[f][v] (the caller's output array), messages
+// msg[f][slot] with the slots of host_build.hpp build_few_layout (class k: base_k + i n_k + j,
+// so a wave's lanes read consecutive doubles for each edge position i) -- and a code may have
+// several degree classes, one check launch per class (the degree is then uniform per launch,
+// as the packed update needs it per wave).  Each message and posterior is the same operation on
+// the same operands as in the frame-parallel kernels, so the bits are the reference's.  The
+// launch boundary is the only synchronisation: no workgroup waits for another.
+constexpr int kFewThreads = 256;
+
+struct FewCheckArgs {
+    const int32_t *checks;  // the class's check ids, ascending
+    int n;                  // its checks
+    int64_t base;           // its first message slot
+    int64_t E, V, C;
+    const int32_t *chk_ptr, *chk_var;
+    const double *post;  // [B][V]
+    double *msg;         // [B][E]
+    const uint8_t *synd;  // [B][C]
+    const uint8_t *active;
+    uint8_t *unsat;
+    const int32_t *finite;  // as CheckArgs
+    const GlibcTables *gglibc;
+};
+
+// decoder.pyx:322-369 for the lane's check, the D messages handed to store(i, c2v_i) with the
+// syndrome sign applied: the packed update for D <= kPackMaxDeg, check_exact's F/B recursion above.
+template <int D, bool FIN, class ST>
+__device__ __forceinline__ void few_update(const double (&m)[D], uint32_t smask, double *wb, const GlibcTablesBP &tab,
+                                           const GlibcK &K, ST store) {
+    if constexpr (kPacked<D>) {
+        double out[D];
+        check_strict_packed<D, FIN ? kClampFinite : kClampFull>(m, out, wb, tab, K);
+#pragma unroll
+        for (int i = 0; i < D; ++i) store(i, apply_sign(out[i], smask));
+    } else {
+        double F[D - 1];
+        F[0] = m[0];
+#pragma unroll
+        for (int i = 1; i < D - 1; ++i) F[i] = box_plus_strict(F[i - 1], m[i], tab, K);
+        store(D - 1, apply_sign(F[D - 2], smask));
+        double Bn = m[D - 1];
+#pragma unroll
+        for (int i = D - 2; i > 0; --i) {
+            store(i, apply_sign(box_plus_strict(F[i - 1], Bn, tab, K), smask));
+            Bn = box_plus_strict(Bn, m[i], tab, K);
+        }
+        store(0, apply_sign(Bn, smask));
+    }
+}
+
+template <int D, int MODE, bool FIN>
+__device__ __forceinline__ void few_check_body(const FewCheckArgs &a, int f, const GlibcTablesBP &tab, double *hb) {
+    const int j0 = (int)(blockIdx.x * kFewThreads + threadIdx.x);
+    if ((j0 & ~63) >= a.n) return;  // wave-uniform: no check left for this wave
+    // surplus lanes of the class's last wave repeat its last check and store nothing
+    const bool live = j0 < a.n;
+    const int j = live ? j0 : a.n - 1;
+    const int cc = a.checks[j];
+    QR_DCHECK(cc >= 0 && cc < a.C && a.chk_ptr[cc + 1] - a.chk_ptr[cc] == D, kDbgFewCheck, cc, j);
+    const int cb = a.chk_ptr[cc];
+    const double *post = a.post + (size_t)f * a.V;
+    double *msg = a.msg + (size_t)f * a.E + a.base + j;  // edge position i at msg[i n]
+    const uint8_t sb = a.synd[(size_t)f * a.C + cc];
+    uint32_t par = sb;
+    double m[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        const int v = a.chk_var[cb + i];
+        QR_DCHECK(v >= 0 && v < a.V, kDbgFewPost, cc, v);
+        QR_DCHECK(a.base + (int64_t)i * a.n + j >= 0 && a.base + (int64_t)i * a.n + j < a.E, kDbgFewSlot, cc, i);
+        const double p = post[v];
+        if (MODE != kFirst) par ^= (p < 0.0) ? 1u : 0u;           // decoder.pyx:243-246
+        if (MODE == kNormal) m[i] = p - msg[(size_t)i * a.n];      // :296-297
+        else m[i] = p;  // first sweep: c2v == 0 and p - 0.0 == p
+    }
+    if (MODE != kFirst && live && par == 1u) a.unsat[f] = 1;  // benign race: every writer stores 1
+    if constexpr (MODE != kParityOnly) {
+        const auto K = GlibcK::pinned();
+        few_update<D, FIN>(m, sign_mask(sb), hb + (threadIdx.x >> 6) * kPackWaveDoubles, tab, K, [&](int i, double x) {
+            if (live) msg[(size_t)i * a.n] = x;  // only this lane reads it back
+        });
+    }
+}
+
+template <int D, int MODE>
+__global__ void __launch_bounds__(kFewThreads) k_few_check(FewCheckArgs a) {
+    __shared__ GlibcTablesBP tab;
+    __shared__ double hb[(kFewThreads / 64) * kPackWaveDoubles];
+    const int f = (int)blockIdx.y;
+    if (!a.active[f]) return;  // block-uniform: the frame has stopped
+    if (MODE != kParityOnly) stage_glibc_tables(&tab, a.gglibc);
+    if constexpr (MODE != kParityOnly && kPacked<D>) {
+        if (sld(a.finite)) {  // kernel-uniform: one of the two bodies runs
+            few_check_body<D, MODE, true>(a, f, tab, hb);
+            return;
+        }
+    }
+    few_check_body<D, MODE, false>(a, f, tab, hb);
+}
+
+struct FewVarArgs {
+    int64_t V, E;
+    const int32_t *var_ptr, *var_slot;
+    const double *lappr;  // [B][V]
+    const double *msg;    // [B][E]
+    double *post;         // [B][V]
+    const uint8_t *active;
+    int32_t *finite;      // INIT: cleared when an input LAPPR is not below fin_bound (null: not computed)
+    double fin_bound;
+};
+
+// decoder.pyx:285-298 for the lane's variable, the sum in ascending edge id.  INIT: as var_block's
+// (lappr + 0.0 on connected variables of frames still decoding, a plain copy for frames that
+// stopped at iteration 0, the batch's finite flag).
+template <bool INIT>
+__global__ void __launch_bounds__(kFewThreads) k_few_var(FewVarArgs a) {
+    const int f = (int)blockIdx.y;
+    const bool act = a.active[f] != 0;
+    if (!INIT && !act) return;  // block-uniform
+    const int64_t v = (int64_t)blockIdx.x * kFewThreads + threadIdx.x;
+    if (v >= a.V) return;
+    const int b = a.var_ptr[v], e = a.var_ptr[v + 1];
+    double p = a.lappr[(size_t)f * a.V + v];
+    if (INIT) {
+        if (a.finite && !(__builtin_fabs(p) < a.fin_bound)) *a.finite = 0;  // every writer stores 0
+        if (act && e > b) p = p + 0.0;
+    } else {
+        const double *msg = a.msg + (size_t)f * a.E;
+        for (int k = b; k < e; ++k) {
+            QR_DCHECK(a.var_slot[k] >= 0 && a.var_slot[k] < a.E, kDbgFewSlot, v, a.var_slot[k]);
+            p += msg[a.var_slot[k]];  // decoder.pyx:292-293
+        }
+    }
+    a.post[(size_t)f * a.V + v] = p;
+}
+
 // Check degrees above the templated range (2..kMaxTemplDeg) take a runtime-degree kernel
 // with no per-lane arrays, so any degree works (the reference sizes its F/B buffer per
 // check, decoder.pyx:131-141): the forward values F_0..F_{d-3} of the reference's
@@ -1387,12 +1534,19 @@ static bool iter_code(const qr_code *code, int ld) {
            code->max_dv <= 64 && (size_t)code->E * ld * sizeof(double) <= ((size_t)1 << 30);
 }
 
+// Knob few_max: qr_decode_frames_device (and with it qr_decode_host) decodes B <= few_max frames
+// of an eligible code with the few-frame schedule (run_few); 0 = off, at most kFewMaxLimit.  The
+// default is the largest batch at which the schedule beat the frame-parallel path of the commit
+// before it on MI355X (scripts/few_frame_rate.py, profiles/few/README.md).
+constexpr int kFewMaxLimit = 64;
+constexpr int kFewMaxDefault = 16;
+
 // Runtime tuning knobs (qr_tune_set); defaults picked by scripts/tune.py on MI355X.
 struct Tuning {
     std::atomic<int> check_ft{128}, check_per{16}, var_ft{128}, var_per{8}, nt{1}, split{3},
         lds_pad_kb{0}, compact{1}, side{1}, min_blocks{2048}, split_min_blocks{1024}, var_pace{28},
         check_tail{4}, fused_iter{1}, iter_streams{2}, var_boost{4}, resident{1}, repack{1},
-        repack_pct{80}, repack_grid{128};
+        repack_pct{80}, repack_grid{128}, few_max{kFewMaxDefault};
 };
 static Tuning g_tune;
 
@@ -2002,6 +2156,157 @@ static int run_resident(const qr_code *code, int B, int ld, const double *lappr,
     return QR_OK;
 }
 
+// decode_batch_device runs this decode frame-resident (k_resident)
+static bool takes_resident(const qr_code *code, int max_it) {
+    return max_it > 0 && max_it <= kResMaxIter && resident_code(code);
+}
+
+// ------------------------------------------------------------------ the few-frame schedule
+// Codes the few-frame sweeps can run: every check degree templated (2..kMaxTemplDeg).
+static bool few_code(const qr_code *code) {
+    for (const auto &c : code->classes)
+        if (c.degree < 2 || c.degree > kMaxTemplDeg) return false;
+    return !code->classes.empty();
+}
+// qr_decode_frames_device decodes these B frames with run_few
+static bool few_route(const qr_code *code, int B, int max_it) {
+    return B <= std::min(g_tune.few_max.load(), kFewMaxLimit) && max_it >= 0 && few_code(code) &&
+           !takes_resident(code, max_it);
+}
+
+// The few-frame workspace: messages msg[B][E], then the flags of the frame-parallel schedules at
+// leading dimension ldf = B rounded up to the wavefront (k_init_status / k_status are reused).
+struct FewWs {
+    double *msg;
+    uint8_t *active, *unsat;
+    int32_t *acount;  // [2] the finite flag, [4, 16) the RangeSel block k_init_status resets
+    size_t bytes;
+};
+static FewWs few_layout(const qr_code *code, int B, int max_it, void *base = nullptr) {
+    FewWs w;
+    Cursor c{(uintptr_t)base};
+    const size_t ldf = align_up((size_t)B, kWave);
+    w.msg = c.take<double>((size_t)code->E * B);
+    w.active = c.take<uint8_t>(ldf);
+    w.unsat = c.take<uint8_t>((size_t)unsat_rows(max_it) * ldf);
+    w.acount = c.take<int32_t>(64);
+    w.bytes = c.off;
+    return w;
+}
+
+struct FewPlan {
+    const qr_code *code;
+    int B, ldf;
+    const double *lappr;
+    const uint8_t *synd;
+    double *post;
+    FewWs w;
+    hipStream_t s;
+};
+
+// One check sweep: a launch per degree class, all named few_check.
+template <int MODE>
+static int launch_few_checks(const FewPlan &P, const double *post_in, uint8_t *unsat) {
+    const qr_code *code = P.code;
+    for (const DegreeClass &cls : code->classes) {
+        FewCheckArgs a;
+        a.checks = cls.d_checks;
+        a.n = (int)cls.n;
+        a.base = cls.few_base;
+        a.E = code->E;
+        a.V = code->V;
+        a.C = code->C;
+        a.chk_ptr = code->d_chk_ptr;
+        a.chk_var = code->d_chk_var;
+        a.post = post_in;
+        a.msg = P.w.msg;
+        a.synd = P.synd;
+        a.active = P.w.active;
+        a.unsat = unsat;
+        a.finite = P.w.acount + 2;
+        a.gglibc = code->d_gtab;
+        const dim3 grid((unsigned)((cls.n + kFewThreads - 1) / kFewThreads), (unsigned)P.B);
+        ProfScope ps("few_check", P.s);
+#define QR_CASE(DD)                                              \
+    case DD:                                                     \
+        k_few_check<DD, MODE><<<grid, kFewThreads, 0, P.s>>>(a); \
+        break;
+        bool handled = true;
+        QR_DEG_SWITCH(cls.degree, QR_CASE, handled)
+#undef QR_CASE
+        if (!handled) return set_error(QR_EVALUE, "decode: no few-frame kernel for degree %d", cls.degree);
+        QR_LAUNCH_CHECK();
+    }
+    return QR_OK;
+}
+
+template <bool INIT>
+static int launch_few_var(const FewPlan &P, int32_t *finite = nullptr, double fin_bound = 0.0) {
+    ProfScope ps(INIT ? "few_var_init" : "few_var", P.s);
+    FewVarArgs a;
+    a.V = P.code->V;
+    a.E = P.code->E;
+    a.var_ptr = P.code->d_var_ptr;
+    a.var_slot = P.code->d_var_msg;
+    a.lappr = P.lappr;
+    a.msg = P.w.msg;
+    a.post = P.post;
+    a.active = P.w.active;
+    a.finite = finite;
+    a.fin_bound = fin_bound;
+    const dim3 grid((unsigned)((P.code->V + kFewThreads - 1) / kFewThreads), (unsigned)P.B);
+    k_few_var<INIT><<<grid, kFewThreads, 0, P.s>>>(a);
+    QR_LAUNCH_CHECK();
+    return QR_OK;
+}
+
+static int launch_few_status(const FewPlan &P, int t, int final_call, int32_t final_iters, const uint8_t *unsat_t,
+                             uint8_t *success, int32_t *iters) {
+    ProfScope ps("status", P.s);
+    k_status<<<(P.B + 255) / 256, 256, 0, P.s>>>(0, P.B, t, final_call, final_iters, unsat_t, P.w.active, success, iters,
+                                                 nullptr, nullptr);
+    QR_LAUNCH_CHECK();
+    return QR_OK;
+}
+
+// decoder.pyx:391-436 on frame-major arrays, in run_flat's order: parity of the input ->
+// status(0) -> first variable sweep -> for t = 1..max_it: C(t), S(t-1), V(t) -> parity of the
+// last posteriors -> final status.  Every data-dependent decision is taken on the device (the
+// sweeps of a stopped frame leave at once), nothing is allocated and nothing waits: one stream,
+// capturable.  The posteriors live in the caller's output array.
+static int run_few(const qr_code *code, int B, const double *lappr, const uint8_t *synd, int max_it, double *final_post,
+                   uint8_t *success, int32_t *iters, void *ws_ptr, hipStream_t s) {
+    FewPlan P{code, B, (int)align_up((size_t)B, kWave), lappr, synd, final_post, few_layout(code, B, max_it, ws_ptr), s};
+    const int ldf = P.ldf;
+    int rc;
+    auto row = [&](int t) { return P.w.unsat + (size_t)t * ldf; };
+    QR_HIP(hipMemsetAsync(P.w.unsat, 0, (size_t)unsat_rows(max_it) * ldf, s));
+    k_init_status<<<(ldf + 255) / 256, 256, 0, s>>>(B, ldf, P.w.active, success, iters, P.w.acount + 2, P.w.acount + 4,
+                                                    ldf / 2, ldf - ldf / 2);
+    QR_LAUNCH_CHECK();
+    const double fin_bound = finite_bound(max_it, code->max_dv);
+    if (fin_bound == 0.0) QR_HIP(hipMemsetAsync(P.w.acount + 2, 0, sizeof(int32_t), s));
+    if ((rc = launch_few_checks<kParityOnly>(P, lappr, row(0)))) return rc;  // decoder.pyx:400-405
+    if ((rc = launch_few_status(P, 0, 0, 0, row(0), success, iters))) return rc;
+    if ((rc = launch_few_var<true>(P, fin_bound > 0.0 ? P.w.acount + 2 : nullptr, fin_bound))) return rc;
+    for (int t = 1; t <= max_it; ++t) {  // decoder.pyx:424-433
+        if (t == 1) {
+            if ((rc = launch_few_checks<kFirst>(P, P.post, row(0)))) return rc;
+        } else {
+            if ((rc = launch_few_checks<kNormal>(P, P.post, row(t - 1)))) return rc;
+            if ((rc = launch_few_status(P, t - 1, 0, 0, row(t - 1), success, iters))) return rc;
+        }
+        if ((rc = launch_few_var<false>(P))) return rc;
+    }
+    if (max_it > 0) {
+        if ((rc = launch_few_checks<kParityOnly>(P, P.post, row(max_it)))) return rc;
+    } else {
+        // decoder.pyx:424 with max_iterations = 0: no sweep, no check -> (0, 0)
+        QR_HIP(hipMemsetAsync(row(0), 1, (size_t)ldf, s));
+    }
+    return launch_few_status(P, max_it, 1, max_it, row(max_it), success, iters);
+}
+
 int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr, const uint8_t *synd, int max_it,
                         double *final_post, uint8_t *success, int32_t *iters, void *ws_ptr, size_t ws_size,
                         hipStream_t s) {
@@ -2013,7 +2318,7 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
     if (ws_size < w.base_bytes)
         return set_error(QR_EVALUE, "decode: workspace too small (%zu < %zu)", ws_size, w.base_bytes);
     DeviceGuard dg(code->device);
-    if (max_it > 0 && max_it <= kResMaxIter && resident_code(code))
+    if (takes_resident(code, max_it))
         return run_resident(code, B, ld, lappr, synd, max_it, final_post, success, iters, w.rsel, s);
     Plan P{code, B, ld, lappr, synd, final_post, success, iters, w, g_tune.nt.load() != 0, s};
     int rc;
@@ -2071,6 +2376,57 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
     }
     if ((rc = launch_status(P, 0, ld, tf, 1, max_it, unsat_last))) return rc;
     return QR_OK;
+}
+
+// ------------------------------------------------------------------ frame-major decode
+// The frame-parallel route of decode_frames_device stages the transposed input and output at the
+// head of the workspace, at ld = B rounded up to the wavefront; decode_batch_device's own
+// workspace follows.
+struct FramesStage {
+    double *lappr_fi, *final_fi;
+    uint8_t *synd_fi;
+    size_t bytes;
+};
+static FramesStage frames_stage(const qr_code *code, int ld, void *base = nullptr) {
+    FramesStage w;
+    Cursor c{(uintptr_t)base};
+    w.lappr_fi = c.take<double>((size_t)code->V * ld);
+    w.final_fi = c.take<double>((size_t)code->V * ld);
+    w.synd_fi = c.take<uint8_t>((size_t)code->C * ld);
+    w.bytes = c.off;
+    return w;
+}
+
+// Room for either route, whatever knob few_max says when the decode is issued.
+static size_t frames_ws_bytes(const qr_code *code, int B, int max_it) {
+    const int ld = (int)align_up((size_t)B, kWave);
+    size_t n = frames_stage(code, ld).bytes + ws_bytes(code, ld, max_it);
+    if (B <= kFewMaxLimit && max_it >= 0 && few_code(code)) n = std::max(n, few_layout(code, B, max_it).bytes);
+    return n;
+}
+
+int decode_frames_device(const qr_code *code, int B, const double *lappr, const uint8_t *synd, int max_it,
+                         double *final_post, uint8_t *success, int32_t *iters, void *ws_ptr, size_t ws_size,
+                         hipStream_t s) {
+    if (B <= 0 || B > INT32_MAX - kWave) return set_error(QR_EVALUE, "decode: B must be positive (B=%d)", B);
+    if (!lappr || !synd || !final_post || !success || !iters || !ws_ptr)
+        return set_error(QR_EVALUE, "decode: null pointer argument");
+    DeviceGuard dg(code->device);
+    if (few_route(code, B, max_it)) {
+        const size_t need = few_layout(code, B, max_it).bytes;
+        if (ws_size < need) return set_error(QR_EVALUE, "decode: workspace too small (%zu < %zu)", ws_size, need);
+        return run_few(code, B, lappr, synd, max_it, final_post, success, iters, ws_ptr, s);
+    }
+    const int ld = (int)align_up((size_t)B, kWave);
+    const FramesStage st = frames_stage(code, ld, ws_ptr);
+    if (ws_size < st.bytes) return set_error(QR_EVALUE, "decode: workspace too small (%zu < %zu)", ws_size, st.bytes);
+    int rc;
+    if ((rc = launch_transpose_to_fi_f64(B, ld, code->V, lappr, st.lappr_fi, s))) return rc;
+    if ((rc = launch_transpose_to_fi_u8(B, ld, code->C, synd, st.synd_fi, s))) return rc;
+    if ((rc = decode_batch_device(code, B, ld, st.lappr_fi, st.synd_fi, max_it, st.final_fi, success, iters,
+                                  (char *)ws_ptr + st.bytes, ws_size - st.bytes, s)))
+        return rc;
+    return launch_transpose_to_fm_f64(B, ld, code->V, st.final_fi, final_post, s);
 }
 
 // ------------------------------------------------- unit-test surface kernels
@@ -2209,18 +2565,13 @@ int qr_code_create(const int64_t *e_to_v, const int64_t *e_to_c, int64_t nv, int
         free_code(code);
         return rc;
     }
-    {
-        // the frame-resident decode's LDS message index of every edge, in the variable CSR's
-        // order: edge i of check c (check-CSR slot chk_ptr[c] + i) lives at i * C + c
-        std::vector<int32_t> msg_of_edge((size_t)E), var_msg((size_t)E);
-        for (int64_t c = 0; c < C; ++c)
-            for (int32_t s = chk_ptr[(size_t)c]; s < chk_ptr[(size_t)c + 1]; ++s)
-                msg_of_edge[(size_t)chk_edge[(size_t)s]] = (int32_t)((s - chk_ptr[(size_t)c]) * C + c);
-        for (int64_t k = 0; k < E; ++k) var_msg[(size_t)k] = msg_of_edge[(size_t)var_edge[(size_t)k]];
-        if ((rc = upload(&code->d_var_msg, var_msg))) {
-            free_code(code);
-            return rc;
-        }
+    // the message slot of every edge in the node-parallel layout, in the variable CSR's order (the
+    // few-frame schedule; a single-class code: i * C + c, the frame-resident decode's LDS index)
+    FewLayout few;
+    build_few_layout(T, few);
+    if ((rc = upload(&code->d_var_msg, few.var_slot))) {
+        free_code(code);
+        return rc;
     }
     {
         std::vector<GlibcTables> gt(1);
@@ -2233,6 +2584,7 @@ int qr_code_create(const int64_t *e_to_v, const int64_t *e_to_c, int64_t nv, int
     for (int d = 0; d < (int)by_deg.size(); ++d) {
         if (by_deg[d].empty()) continue;
         DegreeClass cls{d, (int64_t)by_deg[d].size(), nullptr};
+        cls.few_base = few.classes[code->classes.size()].base;  // the same order: ascending degree
         if (d > kMaxTemplDeg) {
             cls.fb_base = code->fb_rows;
             code->fb_rows += cls.n * (d - 2);
@@ -2302,6 +2654,7 @@ static std::atomic<int> *tune_knob(const char *name) {
         {"fused_iter", &g_tune.fused_iter}, {"iter_streams", &g_tune.iter_streams},
         {"resident", &g_tune.resident},   {"repack", &g_tune.repack},
         {"repack_pct", &g_tune.repack_pct}, {"repack_grid", &g_tune.repack_grid},
+        {"few_max", &g_tune.few_max},
     };
     const std::string n = name ? name : "";
     for (const auto &k : knobs)
@@ -2312,7 +2665,8 @@ static std::atomic<int> *tune_knob(const char *name) {
 int qr_tune_set(const char *name, int64_t value) {
     std::atomic<int> *k = tune_knob(name);
     if (!k) return set_error(QR_EVALUE, "unknown tuning knob '%s'", name ? name : "");
-    if (value < 0 || value > 4096 || (k == &g_tune.split && value != 0 && value != 1 && value != 3))
+    if (value < 0 || value > 4096 || (k == &g_tune.split && value != 0 && value != 1 && value != 3) ||
+        (k == &g_tune.few_max && value > kFewMaxLimit))
         return set_error(QR_EVALUE, "tuning value out of range");
     k->store((int)value);
     return QR_OK;
@@ -2367,31 +2721,42 @@ int qr_decode_batch_device(const qr_code *code, int32_t B, int32_t ld, const dou
                                (hipStream_t)stream);
 }
 
+int qr_decode_frames_workspace_size(const qr_code *code, int32_t B, int32_t max_it, size_t *bytes) {
+    if (!code || !bytes) return set_error(QR_EVALUE, "null argument");
+    if (B <= 0 || B > INT32_MAX - kWave) return set_error(QR_EVALUE, "B must be positive");
+    *bytes = frames_ws_bytes(code, B, max_it);
+    return QR_OK;
+}
+
+int qr_decode_frames_device(const qr_code *code, int32_t B, const double *d_lappr, const uint8_t *d_synd, int32_t max_it,
+                            double *d_final, uint8_t *d_success, int32_t *d_iters, void *ws, size_t ws_size,
+                            void *stream) {
+    if (!code) return set_error(QR_EVALUE, "null code");
+    return decode_frames_device(code, B, d_lappr, d_synd, max_it, d_final, d_success, d_iters, ws, ws_size,
+                                (hipStream_t)stream);
+}
+
 int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, const uint8_t *synd, int32_t max_it,
                    double *final_lappr, uint8_t *success, int32_t *iterations) {
     if (!code) return set_error(QR_EVALUE, "null code");
     if (B <= 0) return set_error(QR_EVALUE, "B must be positive");
-    const int ld = (int)align_up((size_t)B, kWave);
+    if (B > INT32_MAX - kWave) return set_error(QR_EVALUE, "B too large");
     const size_t V = code->V, C = code->C;
-    const size_t wsb = ws_bytes(code, ld, max_it);
+    const size_t wsb = frames_ws_bytes(code, B, max_it);
     DeviceGuard g(code->device);
     std::lock_guard<std::mutex> lk(code->scratch.mu);
-    double *d_fm, *d_lappr, *d_final;  // frame-major staging; frame-innermost input and output
-    uint8_t *d_sfm, *d_synd, *d_succ;
+    double *d_lappr, *d_final;  // frame-major, as the caller's
+    uint8_t *d_synd, *d_succ;
     int32_t *d_it;
     char *d_ws;
-    int rc = code->scratch.take(&d_fm, V * B, &d_lappr, V * ld, &d_final, V * ld, &d_sfm, C * B, &d_synd, C * ld,
-                                &d_succ, (size_t)B, &d_it, (size_t)B, &d_ws, wsb);
+    int rc = code->scratch.take(&d_lappr, V * B, &d_final, V * B, &d_synd, C * B, &d_succ, (size_t)B, &d_it, (size_t)B,
+                                &d_ws, wsb);
     if (rc) return rc;
     hipStream_t s = nullptr;
-    QR_HIP(hipMemcpyAsync(d_fm, lappr, V * B * 8, hipMemcpyHostToDevice, s));
-    QR_HIP(hipMemcpyAsync(d_sfm, synd, C * B, hipMemcpyHostToDevice, s));
-    if ((rc = launch_transpose_to_fi_f64(B, ld, V, d_fm, d_lappr, s))) return rc;
-    if ((rc = launch_transpose_to_fi_u8(B, ld, C, d_sfm, d_synd, s))) return rc;
-    if ((rc = decode_batch_device(code, B, ld, d_lappr, d_synd, max_it, d_final, d_succ, d_it, d_ws, wsb, s)))
-        return rc;
-    if ((rc = launch_transpose_to_fm_f64(B, ld, V, d_final, d_fm, s))) return rc;
-    QR_HIP(hipMemcpyAsync(final_lappr, d_fm, V * B * 8, hipMemcpyDeviceToHost, s));
+    QR_HIP(hipMemcpyAsync(d_lappr, lappr, V * B * 8, hipMemcpyHostToDevice, s));
+    QR_HIP(hipMemcpyAsync(d_synd, synd, C * B, hipMemcpyHostToDevice, s));
+    if ((rc = decode_frames_device(code, B, d_lappr, d_synd, max_it, d_final, d_succ, d_it, d_ws, wsb, s))) return rc;
+    QR_HIP(hipMemcpyAsync(final_lappr, d_final, V * B * 8, hipMemcpyDeviceToHost, s));
     QR_HIP(hipMemcpyAsync(success, d_succ, B, hipMemcpyDeviceToHost, s));
     QR_HIP(hipMemcpyAsync(iterations, d_it, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     QR_HIP(hipStreamSynchronize(s));

@@ -5,6 +5,7 @@
 //   build_tanner_csr   Decoder.__cinit__ / __build_table (decoder.pyx:60-146): O(E) stable
 //                      counting sort of the edge list into int32 CSR per check and per
 //                      variable (ascending edge id), checks grouped by degree;
+//   build_few_layout   the message slots of the node-parallel decodes (frame-resident, few-frame);
 //   build_demap_host   NoiseMapper.__cinit__ tables (noisemapper.pyx:103-236) plus the
 //                      Newton-start and Taylor tables of the fast root search.
 #pragma once
@@ -91,6 +92,40 @@ inline int build_tanner_csr(const int64_t *e_to_v, const int64_t *e_to_c, int64_
     }
     for (int64_t v = 0; v < V; ++v) t.max_dv = std::max(t.max_dv, t.var_ptr[v + 1] - t.var_ptr[v]);
     return QR_OK;
+}
+
+// Message slots of the node-parallel decodes (decoder.hip: k_resident's LDS messages, the
+// few-frame schedule's frame-major msg[f][slot]).  The check classes are the non-empty degrees of
+// by_deg in ascending order; edge position i of the j-th check of class k (n_k checks, the ids of
+// by_deg in ascending order) lives at slot base_k + i n_k + j, base_k = the edges of the classes
+// before k: the lanes of a check sweep (consecutive checks of one class) touch consecutive
+// doubles for each i.  var_slot lists every variable's slots in ascending edge id, indexed by
+// var_ptr like var_edge.  A single-class code gives i C + c.  O(E), no HIP call.
+struct FewClass {
+    int32_t degree;
+    int64_t n, base;
+};
+struct FewLayout {
+    std::vector<FewClass> classes;
+    std::vector<int32_t> var_slot;
+};
+inline void build_few_layout(const TannerCsr &t, FewLayout &L) {
+    L.classes.clear();
+    std::vector<int32_t> slot_of_edge((size_t)t.E);
+    int64_t base = 0;
+    for (size_t d = 0; d < t.by_deg.size(); ++d) {
+        const int64_t n = (int64_t)t.by_deg[d].size();
+        if (!n) continue;
+        for (int64_t j = 0; j < n; ++j) {
+            const int32_t b = t.chk_ptr[(size_t)t.by_deg[d][(size_t)j]];
+            for (int64_t i = 0; i < (int64_t)d; ++i)
+                slot_of_edge[(size_t)t.chk_edge[(size_t)(b + i)]] = (int32_t)(base + i * n + j);
+        }
+        L.classes.push_back(FewClass{(int32_t)d, n, base});
+        base += n * (int64_t)d;
+    }
+    L.var_slot.resize((size_t)t.E);
+    for (int64_t k = 0; k < t.E; ++k) L.var_slot[(size_t)k] = slot_of_edge[(size_t)t.var_edge[(size_t)k]];
 }
 
 // NoiseMapper tables on the host (noisemapper.pyx:103-236) and the fast root search's

@@ -176,6 +176,8 @@ struct DegreeClass {
     // degree > kMaxTemplDeg (runtime-degree kernel): first row of this class's forward
     // values in the decode workspace's F scratch (n * (degree - 2) rows of ld doubles)
     int64_t fb_base = 0;
+    // first message slot of the class in the node-parallel layout (host_build.hpp build_few_layout)
+    int64_t few_base = 0;
 };
 
 struct qr_code {
@@ -189,8 +191,9 @@ struct qr_code {
     // per variable, edge ids ascending.
     int32_t *d_chk_ptr = nullptr, *d_chk_edge = nullptr, *d_chk_var = nullptr;
     int32_t *d_var_ptr = nullptr, *d_var_edge = nullptr;
-    // per variable, edges ascending as above, each given by the frame-resident small-code
-    // decoder's LDS message index i * C + c (edge i of check c)
+    // per variable, edges ascending as above, each given by its message slot in the node-parallel
+    // layout (host_build.hpp build_few_layout: the few-frame schedule's msg[f][slot]; for a
+    // single-class code i * C + c, edge i of check c, the frame-resident decode's LDS index)
     int32_t *d_var_msg = nullptr;
     std::vector<DegreeClass> classes;
     int64_t fb_rows = 0;  // rows of the F scratch (sum over runtime-degree classes)

@@ -42,6 +42,8 @@ SIGNATURES = {
     "qr_decode_workspace_size": [vp, i32, i32, P(C.c_size_t)],
     "qr_decode_batch_device": [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, C.c_size_t, vp],
     "qr_decode_repack_stats": [vp, i32, i32, vp, C.c_size_t, P(C.c_int32)],
+    "qr_decode_frames_workspace_size": [vp, i32, i32, P(C.c_size_t)],
+    "qr_decode_frames_device": [vp, i32, vp, vp, i32, vp, vp, vp, vp, C.c_size_t, vp],
     "qr_decode_host": [vp, i32, vp, vp, i32, vp, vp, vp],
     "qr_check_lappr_host": [vp, vp, vp, vp, vp],
     "qr_check_word_host": [vp, vp, vp, vp, vp],

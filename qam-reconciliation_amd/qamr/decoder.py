@@ -10,6 +10,9 @@ reference, decoder.pyx:135-141).
 Besides the one-frame API, ``decode_batch`` (host arrays, frame-major) and
 ``decode_device`` (torch tensors resident in HBM, frame-innermost layout) decode
 many independent frames per launch -- the path the benchmark measures.
+``decode_frames_device`` takes frame-major tensors in HBM; it, ``decode`` and
+``decode_batch`` run up to knob ``few_max`` frames node-parallel (a lane per check or
+variable of one frame) instead of frame-parallel.
 """
 from __future__ import annotations
 
@@ -240,6 +243,55 @@ class Decoder:
             C.c_void_p(iters.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
             C.c_void_p(stream.cuda_stream)), "decode_device")
         return final_fi, success, iters
+
+    def frames_workspace_bytes(self, B: int, max_iterations: int) -> int:
+        n = C.c_size_t()
+        check(_lib.load().qr_decode_frames_workspace_size(self._h, int(B), int(max_iterations), C.byref(n)))
+        return int(n.value)
+
+    def decode_frames_device(self, lappr, synd, max_iterations: int, final=None, success=None, iters=None,
+                             stream=None):
+        """Decode B frames resident in HBM (torch tensors, frame-major).
+
+        lappr: float64 [B, V]; synd: uint8 [B, C]; any B >= 1.
+        Returns (final float64 [B, V], success uint8 [B], iters int32 [B]).
+        Every tensor must be contiguous and on this decoder's GPU (checked).  Up to knob
+        ``few_max`` frames of a code with check degrees 2..16 run the few-frame schedule on
+        these arrays as they are; other calls go through the frame-innermost decode
+        (transposed inside the workspace).  Asynchronous on ``stream`` (default: torch's
+        current stream), workspace per stream as ``decode_device``."""
+        import torch
+
+        from ._lib import check_tensor
+
+        dev = self._device
+        if not isinstance(lappr, torch.Tensor) or lappr.dim() != 2 or lappr.shape[0] < 1:
+            raise ValueError("decode_frames_device: lappr must be a 2-D tensor [B, V] with B >= 1")
+        B = int(lappr.shape[0])
+        check_tensor(lappr, "lappr", (B, self._V), torch.float64, dev)
+        check_tensor(synd, "synd", (B, self._C), torch.uint8, dev)
+        tdev = lappr.device
+        if final is None:
+            final = torch.empty_like(lappr)
+        if success is None:
+            success = torch.empty(B, dtype=torch.uint8, device=tdev)
+        if iters is None:
+            iters = torch.empty(B, dtype=torch.int32, device=tdev)
+        if not isinstance(final, torch.Tensor) or final.dim() != 2 or final.shape[0] < B:
+            raise ValueError(f"decode_frames_device: final must hold at least B={B} rows of V")
+        check_tensor(final, "final", (final.shape[0], self._V), torch.float64, dev)
+        if success.numel() < B or iters.numel() < B:
+            raise ValueError(f"decode_frames_device: success/iters must hold at least B={B} entries")
+        check_tensor(success, "success", (success.numel(),), torch.uint8, dev)
+        check_tensor(iters, "iters", (iters.numel(),), torch.int32, dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(tdev)
+        ws = self._workspace(stream, self.frames_workspace_bytes(B, max_iterations))
+        check(_lib.load().qr_decode_frames_device(
+            self._h, B, C.c_void_p(lappr.data_ptr()), C.c_void_p(synd.data_ptr()), int(max_iterations),
+            C.c_void_p(final.data_ptr()), C.c_void_p(success.data_ptr()), C.c_void_p(iters.data_ptr()),
+            C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream.cuda_stream)), "decode_frames_device")
+        return final, success, iters
 
     def repack_stats(self, ld: int, max_iterations: int, stream=None):
         """Column repack of the last decode_device on ``stream`` (same ld, max_iterations):
