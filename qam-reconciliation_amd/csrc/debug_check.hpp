@@ -6,10 +6,12 @@
 // (tests/test_gpu_debug_build.py).  The product library compiles every check away.
 //
 // No relocatable device code, so every translation unit that includes this header carries its own
-// counter; it exports one reader built on debug_read_clear, and qr_debug_asserts (decoder.hip)
-// adds them up.  The site numbers are one list across the units: 1..9 decoder.hip (DebugSite),
-// 10..11 grid_interp.hpp (GridDebugSite), 12..16 mi.hip (MiDebugSite), 17..19 decoder.hip again
-// (the few-frame sweeps: 17 lane -> (class, check), 18 gathered posterior index, 19 message slot).
+// counter; a static object of the unit registers its reader (debug_read_clear) in one list
+// (debug_readers, owned by decoder.hip), and qr_debug_asserts (decoder.hip) adds the list up: a
+// unit with checks only has to be compiled with QR_DEBUG_ASSERT (the Makefile's DEBUG_SRCS,
+// tests/test_host_logic.py).  The site numbers are one list across the units: 1..9 and 17..19 the
+// decoder's units (decode_dev.hpp DebugSite), 10..11 grid_interp.hpp (GridDebugSite), 12..16 mi.hip
+// (MiDebugSite).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,19 @@ static bool debug_read_clear(unsigned long long h[4]) {
     return hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dbg), sizeof(z)) == hipSuccess &&
            hipMemcpyToSymbol(HIP_SYMBOL(g_dbg), z, sizeof(z)) == hipSuccess;
 }
+// the readers of every unit of the library that carries checks, in the order the units were linked
+using DebugReader = bool (*)(unsigned long long[4]);
+struct DebugReaders {
+    static constexpr int kMax = 32;  // units; a reader past it is dropped and n still counts it
+    DebugReader fn[kMax];
+    int n = 0;
+    bool add(DebugReader f) {
+        if (n < kMax) fn[n] = f;
+        return ++n <= kMax;
+    }
+};
+DebugReaders &debug_readers();  // decoder.hip (a function-local static: safe at any initialisation order)
+static const bool g_dbg_registered = debug_readers().add(&debug_read_clear);
 }  // namespace qr
 #endif
 

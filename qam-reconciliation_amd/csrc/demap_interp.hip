@@ -136,10 +136,6 @@ int need_grid(const qr_demap *dm) {
     return QR_OK;
 }
 
-#if QR_DEBUG_ASSERT
-int debug_asserts_interp(unsigned long long h[4]) { return debug_read_clear(h) ? QR_OK : QR_EDEVICE; }
-#endif
-
 }  // namespace qr
 
 // ===================================================================== C-ABI

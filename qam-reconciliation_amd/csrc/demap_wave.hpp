@@ -2,9 +2,7 @@
 // (k_mi_terms, k_mi_quad) share: the wave-cooperative root search and the dispatch of a runtime
 // bit_per_symbol to their templates.  Device-side: included by .hip files only.
 #pragma once
-#include <type_traits>
-#include <utility>
-
+#include "qamr_internal.hpp"
 #include "qamr_math.hpp"
 
 namespace qr {
@@ -21,13 +19,9 @@ constexpr int kDemapWaveMaxBps = 6;
 
 // bps in 1..MAX -> f(std::integral_constant<int, bps>), the value as a compile-time constant;
 // false (and no call) outside the range.  Host code.
-template <class F, int... I>
-inline bool dispatch_bps_seq(int bps, F &f, std::integer_sequence<int, I...>) {
-    return ((bps == I + 1 && (f(std::integral_constant<int, I + 1>{}), true)) || ...);
-}
 template <int MAX = kDemapWaveMaxBps, class F>
 inline bool dispatch_bps(int bps, F f) {
-    return dispatch_bps_seq(bps, f, std::make_integer_sequence<int, MAX>{});
+    return dispatch_int_seq<1>(bps, f, std::make_integer_sequence<int, MAX>{});
 }
 
 // rank of this lane among the set lanes of mk below it

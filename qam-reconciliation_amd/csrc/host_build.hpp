@@ -94,7 +94,7 @@ inline int build_tanner_csr(const int64_t *e_to_v, const int64_t *e_to_c, int64_
     return QR_OK;
 }
 
-// Message slots of the node-parallel decodes (decoder.hip: k_resident's LDS messages, the
+// Message slots of the node-parallel decodes (decode_small.hip: k_resident's LDS messages; decode_few.hip: the
 // few-frame schedule's frame-major msg[f][slot]).  The check classes are the non-empty degrees of
 // by_deg in ascending order; edge position i of the j-th check of class k (n_k checks, the ids of
 // by_deg in ascending order) lives at slot base_k + i n_k + j, base_k = the edges of the classes

@@ -350,11 +350,6 @@ struct DevBuf {
 // {rounds, launches, work items, host bookkeeping ns, wall ns} of this thread's last qr_mi_quad_batch
 static thread_local int64_t g_quad_stats[5];
 
-
-#if QR_DEBUG_ASSERT
-int debug_asserts_mi(unsigned long long h[4]) { return debug_read_clear(h) ? QR_OK : QR_EDEVICE; }
-#endif
-
 }  // namespace qr
 
 // ===================================================================== C-ABI

@@ -6,6 +6,8 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "qamr.h"
@@ -44,6 +46,14 @@ bool profiling_on();
 constexpr int kWave = 64;
 inline int frame_tile(int ld) { return (ld % 256 == 0) ? 256 : (ld % 128 == 0) ? 128 : 64; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// v in LO..LO+N-1 -> f(std::integral_constant<int, v>{}), the value as a compile-time constant;
+// false (and no call) outside the range.  Under dispatch_bps (demap_wave.hpp) and dispatch_degree
+// (decode_dev.hpp).
+template <int LO, class F, int... I>
+inline bool dispatch_int_seq(int v, F &f, std::integer_sequence<int, I...>) {
+    return ((v == LO + I && (f(std::integral_constant<int, LO + I>{}), true)) || ...);
+}
 
 // Bump cursor over a device buffer: take<T>(n) is the next n elements of T, 256-byte aligned.
 // With a null base it only measures: every take is null and off counts the bytes walked.
@@ -108,15 +118,10 @@ bool grid_fast(const qr_demap *dm);                       // demap_interp.hip: b
 int need_grid(const qr_demap *dm);                        // demap_interp.hip: an error unless the grid was created
 
 // Debug build (libqamr_debug.so, QR_DEBUG_ASSERT=1): device-side index checks (debug_check.hpp).
-// Every unit that carries checks counts its own failures and exports one reader: h = {failed
-// checks, first site, first a, first b}, read and cleared; qr_debug_asserts (decoder.hip) reports
-// their sum and the first failing site in the order decoder.hip, demap_interp.hip, mi.hip.
+// Every unit that carries checks counts its own failures and registers its reader there;
+// qr_debug_asserts (decoder.hip) reports their sum and the first failing unit's site.
 #ifndef QR_DEBUG_ASSERT
 #define QR_DEBUG_ASSERT 0
-#endif
-#if QR_DEBUG_ASSERT
-int debug_asserts_interp(unsigned long long h[4]);   // demap_interp.hip
-int debug_asserts_mi(unsigned long long h[4]);       // mi.hip
 #endif
 
 struct DeviceGuard {
@@ -199,7 +204,7 @@ struct qr_code {
     int64_t fb_rows = 0;  // rows of the F scratch (sum over runtime-degree classes)
     qr::GlibcTables *d_gtab = nullptr; // strict box-plus: glibc exp/log data (glibc_math.hpp)
     mutable qr::Scratch scratch;
-    // two-stream schedule (decoder.hip run_split2): a second stream for the variable
+    // two-stream schedule (decoder.hip run_split2; run_iter, decode_small.hip): a second stream for the variable
     // sweeps and the events that order the two; created on first use, guarded by mu
     // while a decode enqueues (concurrent decodes on one code enqueue one at a time).
     mutable std::mutex mu;

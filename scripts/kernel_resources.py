@@ -5,7 +5,7 @@ note): name, VGPRs allocated (.vgpr_count), SGPRs, scratch bytes per lane, LDS b
 
     python scripts/kernel_resources.py [qam-reconciliation_amd/qamr/libqamr.so] [--filter k_repack]
 
-Used by tests/test_vgpr_budget.py (the register note of decoder.hip: kernels launched beside the
+Used by tests/test_vgpr_budget.py (the register note of decode_repack.hip: kernels launched beside the
 check sweep allocate 16 or 32 VGPRs, never 24)."""
 from __future__ import annotations
 

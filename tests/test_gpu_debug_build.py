@@ -1,7 +1,7 @@
 """The device-asserting debug build (the reference compiles with bounds checks off,
 decoder.pyx:181,240,289,332,399,411, so the port adds them).  `make -C qam-reconciliation_amd/csrc
 DEBUG=1` (also part of the default build) makes qamr/libqamr_debug.so: libqamr with QR_DEBUG_ASSERT
-index checks (decoder.hip QR_DCHECK) on the column repack's active-frame list, frame ids and row-group
+index checks (QR_DCHECK in decoder.hip, decode_repack.hip and decode_small.hip) on the column repack's active-frame list, frame ids and row-group
 slots (k_repack_rows, k_repack_output), the active-frame list writes (k_compact) and reads
 (lane_frame), the narrow sweeps' lane -> (node, frame) mapping, and the frame-resident decode's LDS
 posterior and message indices (k_resident).  This test runs the repack parity tests (the bench's

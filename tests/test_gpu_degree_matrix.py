@@ -1,6 +1,6 @@
 """Check degrees 2..16 in every decode schedule, in both clamp variants.
 
-decoder.hip instantiates its check update per degree: ``k_check<D>`` for D = 2..16 (the
+The decoder (decoder.hip, decode_small.hip) instantiates its check update per degree: ``k_check<D>`` for D = 2..16 (the
 frame-parallel sweep of the lock-step and two-stream schedules, with the repack's transition
 mapping), and ``check_narrow<D>``, ``k_iter<D>`` and ``k_resident<D>`` for D = 2..10
 (kPackMaxDeg); the packed update's rounds (strict_pack.hpp) are laid out at compile time from D,
@@ -39,7 +39,7 @@ MI = 30
 PAD = 7.0
 NEVER = ((0, 0), (LD // 2, LD // 2))
 DEGREES = tuple(range(2, 17))
-PACK_MAX = 10   # decoder.hip kPackMaxDeg: narrow sweeps, k_iter and k_resident exist up to here
+PACK_MAX = 10   # decode_dev.hpp kPackMaxDeg: narrow sweeps, k_iter and k_resident exist up to here
 
 
 def v_of(D):

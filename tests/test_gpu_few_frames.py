@@ -1,4 +1,4 @@
-"""The few-frame decode schedule (decoder.hip run_few: k_few_check, k_few_var) and the frame-major
+"""The few-frame decode schedule (decode_few.hip run_few: k_few_check, k_few_var) and the frame-major
 device entry point qr_decode_frames_device / Decoder.decode_frames_device.
 
 Every frame of every decode is compared with the oracle (oracle/qamr_oracle.c): success flag,

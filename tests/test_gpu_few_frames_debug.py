@@ -1,6 +1,6 @@
 """The few-frame sweeps on the device-asserting debug build (libqamr_debug.so, QR_DEBUG_ASSERT:
 tests/test_gpu_debug_build.py).  Their QR_DCHECKs cover every gathered posterior index, every
-message slot (check and variable sweeps) and the lane -> (class, check) mapping (decoder.hip
+message slot (check and variable sweeps) and the lane -> (class, check) mapping (decode_few.hip,
 DebugSite 17..19).  A child process on that library runs the mixed-class, routing, sizing and
 graph-capture tests of tests/test_gpu_few_frames.py and degrees 2, 8 and 15 of its degree matrix;
 conftest's autouse fixture fails any test after which a device check failed."""

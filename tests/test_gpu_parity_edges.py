@@ -190,7 +190,7 @@ def test_device_api_argument_checks(gpu):
 
 def _check_regular_irregular_var(N, dc, seed):
     """One check-degree class (dc) with variable degrees 1..5 and parallel edges: the codes the
-    one-launch-per-iteration schedule (decoder.hip k_iter) runs."""
+    one-launch-per-iteration schedule (decode_small.hip k_iter) runs."""
     rng = np.random.default_rng(seed)
     dv = rng.integers(1, 6, N)
     sockets = np.repeat(np.arange(N), dv)

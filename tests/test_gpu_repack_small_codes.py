@@ -21,7 +21,7 @@ Every frame of every run is compared with the oracle (oracle/qamr_oracle.c): suc
 iteration count and final LAPPRs bit for bit.  The inputs are conditioned on the CPU: from the
 oracle's (success, iterations) alone each range's running-frame count drops to at most 80 % of
 its 256 columns before the last decision point, and the repacks the device must then decide
-(``_predict``: the rule of decoder.hip repack_go applied to the oracle's counts) are compared
+(``_predict``: the rule of decode_repack.hip repack_go applied to the oracle's counts) are compared
 with ``Decoder.repack_stats``.
 """
 import functools
@@ -130,7 +130,7 @@ def _predict(succ, its, B, mi, pct=80):
     """((repacks 0, repacks 1), (width 0, width 1)) the device must end with: the decision point
     before a range's variable sweep t < mi reads the count its status launch of iteration t - 1
     wrote, and repacks to max(64, count rounded up to 64) when the count is at most pct % of the
-    width and that is narrower (decoder.hip repack_go)."""
+    width and that is narrower (decode_repack.hip repack_go)."""
     reps, ws = [], []
     for k in range(2):
         w, rep = H, 0

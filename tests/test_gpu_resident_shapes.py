@@ -1,7 +1,7 @@
 """The frame-resident decode past one pass of its 512 threads, variables with no edge, and the
 boundaries at which a code changes path.
 
-* ``k_resident`` (decoder.hip) holds a frame's messages and posteriors in 8 (E + V) bytes of
+* ``k_resident`` (decode_small.hip) holds a frame's messages and posteriors in 8 (E + V) bytes of
   dynamic LDS, at most 36 KiB, so V up to 2304 and C up to 1152: more than one pass of its check
   loop (512 checks a pass) and of its variable loop (1024 variables a trip), the ``lreg == false``
   path (V > 1024: LAPPRs re-read per iteration, the register path of regular variable degrees <= 3
@@ -267,7 +267,7 @@ def test_isolated_variables_keep_input_bits(gpu):
 
 
 def test_resident_lds_boundary(gpu):
-    """resident_code (decoder.hip): a code is frame-resident when 8 (E + V) + kResStaticLds <=
+    """resident_code (decode_small.hip): a code is frame-resident when 8 (E + V) + kResStaticLds <=
     min(80 KiB, the device's LDS per workgroup), kResStaticLds = 8192 + 8 * 576 * 8 = 45056, so
     E + V <= 4608.  Control first: regular_code(1008) (E + V = 4032) is resident (it would not be
     on a device that gives a workgroup less LDS than the rule assumes).  regular_code(1539, 2, 3)
@@ -285,7 +285,7 @@ def test_resident_lds_boundary(gpu):
 
 @pytest.mark.parametrize("hub", [64, 66])
 def test_max_var_degree_boundary(gpu, hub):
-    """iter_code (decoder.hip) takes max_dv <= 64.  401 variables, variable 0 of degree 64, the
+    """iter_code (decode_small.hip) takes max_dv <= 64.  401 variables, variable 0 of degree 64, the
     others of degree 2, dealt 6 per check (E = 864, C = 144): resident = 0 runs iter_d6.  400
     variables, variable 0 of degree 66, dealt 3 per check (E = 864, C = 288): resident = 0 runs
     the flat schedule (check_d3, no iter_d3).  Both are frame-resident under default knobs (a 64-

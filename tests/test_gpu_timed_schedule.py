@@ -27,7 +27,7 @@ import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-# the tuning bench.py runs with (csrc/decoder.hip Tuning defaults)
+# the tuning bench.py runs with (csrc/decode_host.hpp Tuning defaults)
 TIMED = dict(split=3, compact=1)
 
 

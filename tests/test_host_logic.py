@@ -89,3 +89,27 @@ def test_noisemapper_module_functions_vs_reference():
     assert_bit_exact(getattr(nmod, "__view_dist_cut")(g["x"]), g["dist_cut"])
     with pytest.raises(ValueError):
         nmod.F_Z(g["z"].astype(np.float32), 0.0, 1.0)
+
+
+def test_debug_srcs_lists_every_unit_with_device_checks():
+    """csrc/Makefile DEBUG_SRCS (the units libqamr_debug.so compiles with QR_DEBUG_ASSERT) is exactly
+    the set of csrc/*.hip whose own text, or a project header they include directly, contains
+    ``QR_DCHECK(``: a unit left out would carry checks that are compiled away and never read.
+    debug_check.hpp defines the macro, so including it directly counts: such a unit registers a
+    counter with qr_debug_asserts whether or not it has a check site of its own yet."""
+    import glob
+    import re
+
+    csrc = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
+    read = lambda p: open(p, encoding="utf-8").read()
+    listed = re.search(r"^DEBUG_SRCS\s*:=\s*((?:.*\\\n)*.*)$", read(os.path.join(csrc, "Makefile")), re.M).group(1)
+    listed = set(listed.replace("\\\n", " ").split())
+    need = set()
+    for unit in glob.glob(os.path.join(csrc, "*.hip")):
+        texts = [read(unit)]
+        for h in re.findall(r'^#include "([^"]+)"', texts[0], re.M):
+            if os.path.exists(os.path.join(csrc, h)):
+                texts.append(read(os.path.join(csrc, h)))
+        if any("QR_DCHECK(" in t for t in texts):
+            need.add(os.path.basename(unit))
+    assert need and listed == need, (sorted(listed - need), sorted(need - listed))

@@ -1,4 +1,4 @@
-"""The register note of decoder.hip as a guard (CPU: reads the built gfx950 code object).
+"""The register note of decode_repack.hip as a guard (CPU: reads the built gfx950 code object).
 
 On MI355X the kernels that run on the variable stream BESIDE the degree-7 check sweep -- the
 paced variable sweep k_var and the repack decision / row-move kernel k_repack_rows -- must
