@@ -14,12 +14,13 @@ import functools
 
 import numpy as np
 
+import decode_fixture as DF
 import oracle as O
 
 MI = 30
 MIS = (0, 1, 2, MI)
 PAD = 7.0
-SPECIAL5 = [np.inf, -np.inf, -0.0, 0.0, np.nan]
+SPECIAL5 = DF.SPECIAL5
 ISOLATED4 = [-0.0, np.nan, np.inf, -np.inf]
 
 MIXED_V = 702
@@ -51,15 +52,6 @@ def mixed_code():
 
 def mixed_isolated():
     return np.array([v for v in range(MIXED_V) if v % 6 == 2])
-
-
-def _draw(orc, rng, n, sigma):
-    V = orc.vnum
-    word = rng.integers(0, 2, (n, V)).astype(np.uint8)
-    synd = np.stack([orc.eval_syndrome(w) for w in word])
-    sig = rng.uniform(*sigma, n)[:, None]
-    llr = 2 / sig ** 2 * ((1 - 2.0 * word) + sig * rng.standard_normal((n, V)))
-    return word, synd, sig, llr
 
 
 def _pick(orc, word, synd, sig, llr, special_first5):
@@ -104,17 +96,12 @@ def assert_conditions(ref, frames=slice(None)):
 
 @functools.lru_cache(maxsize=None)
 def degree_case(D, variant):
-    import test_gpu_degree_matrix as M
-
-    base = M.case_of(D, "clean")  # its first 64 frames, exactly as that file draws them
-    orc, V = base["orc"], M.v_of(D)
-    rng = np.random.default_rng(1000 + D)  # the same stream again, for the words and sigmas
-    word = rng.integers(0, 2, (M.LD, V)).astype(np.uint8)
-    sig = rng.uniform(*M.sigma_of(D), M.LD)[:, None]
-    llr, synd = base["llr"][:64], base["synd"][:64]
+    base = DF.case_of(D, "clean")  # the degree matrix's case: its first 64 frames
+    orc = base["orc"]
+    llr, synd, word, sig = (base[k][:64] for k in ("llr", "synd", "word", "sig"))
     assert np.array_equal(synd[0], orc.eval_syndrome(word[0]))
     assert variant in ("clean", "special")
-    L, S = _pick(orc, word[:64], synd, sig[:64], llr, variant == "special")
+    L, S = _pick(orc, word, synd, sig, llr, variant == "special")
     assert np.isfinite(L).all() == (variant == "clean")
     return _finish(base["vid"], base["cid"], orc, L, S)
 
@@ -133,7 +120,7 @@ def mixed_case():
     assert vdeg[0] == MIXED_HUB_DEGREE > 64 and (vdeg[mixed_isolated()] == 0).all()
     assert abs(mixed_isolated().size - MIXED_V / 6) < 2
     rng = np.random.default_rng(MIXED_SEED + 1)
-    word, synd, sig, llr = _draw(orc, rng, 48, MIXED_SIGMA)
+    llr, synd, word, sig = DF.draw_frames(orc, rng, 48, MIXED_SIGMA)
     L, S = _pick(orc, word, synd, sig, llr, False)
     L[1:, mixed_isolated()[:4]] = ISOLATED4
     return _finish(vid, cid, orc, L, S)

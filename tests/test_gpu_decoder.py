@@ -10,6 +10,7 @@ import pytest
 from conftest import GOLDEN, assert_bit_exact, golden
 
 import oracle as O
+from decode_fixture import knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -237,7 +238,7 @@ def test_decode_device_graph_capture(gpu):
     stream forks from and joins the caller's stream through events) is capturable in a
     HIP graph: the replay reproduces the eager decode bit for bit."""
     import torch
-    from qamr import _lib, codes
+    from qamr import codes
 
     vid, cid = codes.regular_code(1008)
     dec = _decoder(vid, cid)
@@ -250,10 +251,8 @@ def test_decode_device_graph_capture(gpu):
     llr = 2 / sig ** 2 * ((1 - 2.0 * word) + sig * rng.standard_normal((B, 1008)))
     L = torch.from_numpy(llr.T.copy()).cuda()
     S = torch.from_numpy(synd.T.copy()).cuda()
-    saved = _lib.tune_get("split")
-    try:
-        for split in (3, 1):
-            _lib.tune_set("split", split)
+    for split in (3, 1):
+        with knobs(split=split):
             ref = [x.clone() for x in dec.decode_device(L, S, B, 30)]  # eager (also allocates)
             fin = torch.full_like(L, np.nan)
             succ = torch.zeros(B, dtype=torch.uint8, device="cuda")
@@ -264,10 +263,8 @@ def test_decode_device_graph_capture(gpu):
                 dec.decode_device(L, S, B, 30, fin, succ, its)
             g.replay()
             torch.cuda.synchronize()
-            assert torch.equal(succ, ref[1]) and torch.equal(its, ref[2]), split
-            assert torch.equal(fin.view(torch.int64), ref[0].view(torch.int64)), split
-    finally:
-        _lib.tune_set("split", saved)
+        assert torch.equal(succ, ref[1]) and torch.equal(its, ref[2]), split
+        assert torch.equal(fin.view(torch.int64), ref[0].view(torch.int64)), split
 
 
 def test_strict_clamp_paths(gpu):

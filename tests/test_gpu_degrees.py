@@ -9,6 +9,7 @@ import pytest
 from conftest import assert_bit_exact
 
 import oracle as O
+from decode_fixture import knobs, scattered_code
 
 pytestmark = pytest.mark.gpu
 
@@ -19,12 +20,7 @@ def _code(rng, degrees, V):
     E0 = int(sum(degrees))
     extra = max(0, V - E0)
     degrees += [3] * ((extra + 2) // 3)
-    deg = np.array(degrees)
-    E = int(deg.sum())
-    sockets = np.concatenate([np.arange(V), rng.integers(0, V, E - V)])
-    rng.shuffle(sockets)
-    cid = np.repeat(np.arange(len(deg)), deg)
-    return sockets.astype(np.int64), cid.astype(np.int64)
+    return scattered_code(rng, degrees, V)
 
 
 def _frames(rng, orc, B, V, sig=(0.5, 0.9)):
@@ -48,12 +44,8 @@ def test_high_degree_checks_vs_oracle(gpu, split):
     dec = qamr.Decoder(vid, cid)
     orc = O.OracleCode(vid, cid)
     llr, synd = _frames(rng, orc, 70, V)
-    old = qamr._lib.tune_get("split")
-    try:
-        qamr._lib.tune_set("split", split)
+    with knobs(split=split):
         s1, i1, f1 = dec.decode_batch(llr, synd, 30)
-    finally:
-        qamr._lib.tune_set("split", old)
     s2, i2, f2 = orc.decode_batch(llr, synd, 30)
     assert np.array_equal(s1, s2) and np.array_equal(i1, i2)
     assert_bit_exact(f1, f2)
@@ -82,18 +74,14 @@ def test_workspace_bytes_closed_form(gpu):
 
     high = _high_degree_code(np.random.default_rng(17))
     cases = [(codes.regular_code(1008), 64), (codes.regular_code(1008), 512), (high, 128)]
-    saved = qamr._lib.tune_get("repack")
-    try:
-        for repack in (1, 0):
-            qamr._lib.tune_set("repack", repack)
+    for repack in (1, 0):
+        with knobs(repack=repack):
             for (vid, cid), ld in cases:
                 dec = qamr.Decoder(vid, cid)
                 for max_it in (0, 30):
                     want, fb_rows, iter_code = _workspace_closed_form(vid, cid, ld, max_it, repack)
                     assert (fb_rows > 0) == (vid is high[0]) and iter_code == (vid is not high[0])
                     assert dec.workspace_bytes(ld, max_it) == want, (vid.size, ld, max_it, repack)
-    finally:
-        qamr._lib.tune_set("repack", saved)
 
 
 def test_degree_255_and_all_large(gpu):

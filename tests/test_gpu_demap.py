@@ -8,6 +8,7 @@ import pytest
 from conftest import assert_bit_exact, assert_llr_close, golden
 
 import oracle as O
+from decode_fixture import knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -159,7 +160,6 @@ def test_fast_root_search_bit_identical_to_brute_force(gpu, bps, snr):
     the reference's brute-force bracket + bisection (qr_tune demap_fast=0) on every
     symbol: uniform n_hat, the edge values 0 / 1 / tiny, both sign configurations."""
     import torch
-    from qamr import _lib
 
     pa = __import__("qamr").PAMAlphabet(bps, 2.0)
     nv = pa.variance * 10 ** (-snr / 10) / 2
@@ -175,13 +175,10 @@ def test_fast_root_search_bit_identical_to_brute_force(gpu, bps, snr):
     dev = torch.device("cuda", 0)
     nt = torch.from_numpy(n).to(dev).contiguous()
     xt = torch.from_numpy(x).to(dev).contiguous()
-    try:
-        _lib.tune_set("demap_fast", 1)
+    with knobs(demap_fast=1):
         fast = nm.demap_device(nt, xt, ld).clone()
-        _lib.tune_set("demap_fast", 0)
+    with knobs(demap_fast=0):
         brute = nm.demap_device(nt, xt, ld).clone()
-    finally:
-        _lib.tune_set("demap_fast", 1)
     torch.cuda.synchronize()
     a, b = fast.cpu().numpy(), brute.cpu().numpy()
     same = (a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))
@@ -196,7 +193,6 @@ def test_wave_private_demap_equals_per_symbol(gpu, bps, snr):
     indices (-> NaN) and both sign configurations; and its output matches the oracle
     (reference restatement) on sampled frames."""
     import torch
-    from qamr import _lib
 
     pa = __import__("qamr").PAMAlphabet(bps, 2.0)
     nv = pa.variance * 10 ** (-snr / 10) / 2
@@ -212,14 +208,10 @@ def test_wave_private_demap_equals_per_symbol(gpu, bps, snr):
     dev = torch.device("cuda", 0)
     nt = torch.from_numpy(n).to(dev).contiguous()
     xt = torch.from_numpy(x).to(dev).contiguous()
-    saved = _lib.tune_get("demap_hyp")
-    try:
-        _lib.tune_set("demap_hyp", 1)   # wave-private (default): one wave walks all hypotheses of its tile
+    with knobs(demap_hyp=1):   # wave-private (default): one wave walks all hypotheses of its tile
         wav = nm.demap_device(nt, xt, B, alpha=0.5).clone()
-        _lib.tune_set("demap_hyp", 0)   # one lane per symbol
+    with knobs(demap_hyp=0):   # one lane per symbol
         per = nm.demap_device(nt, xt, B, alpha=0.5).clone()
-    finally:
-        _lib.tune_set("demap_hyp", saved)
     torch.cuda.synchronize()
     b = per[:, :B].cpu().numpy()
     a = wav[:, :B].cpu().numpy()
@@ -278,7 +270,6 @@ def test_noise_search_random_vs_oracle_and_errors(gpu):
     at width == y_accuracy), fast vs brute search identical, the oracle as checker; out-of-range
     i -> NaN; size / dtype mismatch -> ValueError (noisemapper.pyx:410-411)."""
     import qamr
-    from qamr import _lib
     rng = np.random.default_rng(17)
     for bps, nv in ((2, 0.35), (3, 0.8), (4, 0.05)):
         M = 1 << bps
@@ -290,12 +281,8 @@ def test_noise_search_random_vs_oracle_and_errors(gpu):
         for acc in (1e-3, 2.0 ** -20, 1e-9, 3e-11):
             got = nm.demap_noise_search(n, i, acc)
             assert_bit_exact(got, [onm.g_inv_search(a, b, acc) for a, b in zip(n, i)])
-        saved = _lib.tune_get("demap_fast")
-        try:
-            _lib.tune_set("demap_fast", 0)
+        with knobs(demap_fast=0):
             brute = nm.demap_noise_search(n, i)
-        finally:
-            _lib.tune_set("demap_fast", saved)
         assert_bit_exact(nm.demap_noise_search(n, i), brute)
     nm = _nm(2, 1.0)
     assert np.isnan(nm.demap_noise_search(np.array([0.5, 0.5]), np.array([-1, 4], np.int64))).all()

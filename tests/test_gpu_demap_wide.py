@@ -6,7 +6,6 @@ build_demap_host drops the Taylor table and Newton runs on the component sums.  
 the root search each case reaches is reported and asserted on the host by
 tests/test_demap_replay.py::test_fast_search_bit_identical_wide.  Everything is bit for bit
 (conftest.assert_bit_exact: infinities and the NaN pattern included)."""
-import contextlib
 import functools
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 from conftest import assert_bit_exact, golden
 
 import oracle as O
+from decode_fixture import knobs
 
 import make_golden_cases as MC
 
@@ -38,20 +38,6 @@ def _nm(c, base):
     k = f"c{c}_"
     return qamr.NoiseMapper(qamr.PAMAlphabet(int(g[k + "bps"]), 2.0, g[k + "probs"]), float(g[k + "noise_var"]),
                             None if base else g[k + "cfg"])
-
-
-@contextlib.contextmanager
-def _knobs(**kv):
-    """Set the demapper's tuning knobs; the saved values come back on exit."""
-    from qamr import _lib
-    saved = {k: _lib.tune_get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            _lib.tune_set(k, v)
-        yield
-    finally:
-        for k, v in saved.items():
-            _lib.tune_set(k, v)
 
 
 def _padded_block(n, j, M, ld):
@@ -109,7 +95,7 @@ def test_device_entry_vs_reference(gpu, c, setting):
     n, j = g[k + "n"], g[k + "j"].astype(np.int64)
     S, B = n.shape
     hyp, fast = SETTINGS[setting]
-    with _knobs(demap_hyp=hyp, demap_fast=fast):
+    with knobs(demap_hyp=hyp, demap_fast=fast):
         got = _device_demap(nm, n, j, ALPHA)
     # la[(s * B + f) * bps + k] -> row s * bps + k, column f
     ref = (g[k + "la"] * ALPHA).reshape(S, B, bps).transpose(0, 2, 1).reshape(S * bps, B)
@@ -127,7 +113,7 @@ def test_root_search_vs_reference(gpu, c):
         nm = _nm(c, base)
         ref = g[k + ("base_dns" if base else "dns")]
         for fast in (1, 0):
-            with _knobs(demap_fast=fast):
+            with knobs(demap_fast=fast):
                 got = nm.demap_noise_search(n, di)
             assert_bit_exact(got, ref)
 

@@ -6,7 +6,7 @@ iteration count and final LAPPRs bit for bit; the output is allocated with one e
 with a pad value that must stay untouched.  Which path ran is read from the profiling counters of
 the same decode: the few-frame launches are named ``few_check`` / ``few_var`` / ``few_var_init``,
 the frame-parallel ones ``check1_dD`` / ``check_dD`` / ``iter_dD`` / ``resident_dD``.  Knobs are
-set explicitly (``few_max = 8`` unless a case says otherwise) and restored in a finally.
+set explicitly (``few_max = 8`` unless a case says otherwise) under decode_fixture.knobs.
 
 1. degree matrix: regular (3, D) codes, D = 2..16, finite and special inputs, 5 frames with a
    codeword, an early and a late stop, at max_iterations 0, 1, 2, 30;
@@ -23,10 +23,10 @@ from conftest import assert_bit_exact
 
 import few_fixture as F
 import oracle as O
+from decode_fixture import knobs, profiled
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("few_max", "resident")
 FRAME_PARALLEL = ("check", "check1", "iter", "resident")
 
 
@@ -58,20 +58,15 @@ def _decode(dec, llr, synd, mi, ref, tag, **kw):
     """One decode_frames_device of the given frames into an output of B + 1 rows; returns the
     launch counters of the decode."""
     import torch
-    from qamr import _lib
 
     B = llr.shape[0]
     L = torch.from_numpy(np.array(llr)).cuda()   # (copies: the cases are read-only)
     S = torch.from_numpy(np.array(synd)).cuda()
     fin =torch.full((B + 1, llr.shape[1]), F.PAD, dtype=torch.float64, device="cuda")
-    _lib.profile_enable(True)
-    _lib.profile_reset()
-    try:
+    with profiled():
         _, succ, its = dec.decode_frames_device(L, S, mi, final=fin, **kw)
         torch.cuda.synchronize()
         n = _counters()
-    finally:
-        _lib.profile_enable(False)
     s2, i2, f2 = ref
     print(tag, n, succ.cpu().numpy(), its.cpu().numpy())
     assert np.array_equal(succ.cpu().numpy(), s2), tag
@@ -79,26 +74,6 @@ def _decode(dec, llr, synd, mi, ref, tag, **kw):
     assert_bit_exact(fin[:B].cpu().numpy(), f2)
     assert bool((fin[B] == F.PAD).all()), tag
     return n
-
-
-class _Knobs:
-    """Set the knobs on entry, restore what they were on exit."""
-
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        from qamr import _lib
-
-        self.saved = {k: _lib.tune_get(k) for k in KNOBS}
-        for k, v in self.kw.items():
-            _lib.tune_set(k, v)
-
-    def __exit__(self, *exc):
-        from qamr import _lib
-
-        for k, v in self.saved.items():
-            _lib.tune_set(k, v)
 
 
 # ------------------------------------------------------------------ 1. degree matrix
@@ -111,7 +86,7 @@ def test_few_degree_matrix_vs_oracle(gpu, D, variant):
     F.assert_conditions(case["ref"])
     dec = qamr.Decoder(case["vid"], case["cid"])
     assert dec.max_check_degree == D
-    with _Knobs(few_max=8, resident=0):
+    with knobs(few_max=8, resident=0):
         for mi in F.MIS:
             n = _decode(dec, case["llr"], case["synd"], mi, case["ref"][mi], (D, variant, mi))
             _assert_few(n, mi)
@@ -127,7 +102,7 @@ def test_few_mixed_classes_vs_oracle(gpu, B):
     dec = qamr.Decoder(case["vid"], case["cid"])
     assert dec.max_check_degree == 16 and dec.max_var_degree == F.MIXED_HUB_DEGREE
     iso = F.mixed_isolated()[:4]
-    with _Knobs(few_max=8, resident=1):  # several classes: never frame-resident
+    with knobs(few_max=8, resident=1):  # several classes: never frame-resident
         for mi in F.MIS:
             ref = tuple(a[:B] for a in case["ref"][mi])
             if B > 1:  # the isolated variables keep their input bits
@@ -156,7 +131,7 @@ def test_few_dvbs2_vs_oracle(gpu):
     runs all 50 iterations) as B = 1: through decode_frames_device, and through the drop-in's
     Decoder.decode / decode_batch (qr_decode_host), which take the same path."""
     import qamr
-    from qamr import _lib, codes
+    from qamr import codes
 
     vid, cid = codes.dvbs2_like_half()
     dec = qamr.Decoder(vid, cid)
@@ -166,17 +141,13 @@ def test_few_dvbs2_vs_oracle(gpu):
     ref3, ref1 = orc.decode_batch(L3, S3, 50), orc.decode_batch(L1, S1, 50)
     print("oracle", ref3[0], ref3[1], ref1[0], ref1[1])
     assert ref3[0].all() and len(set(ref3[1].tolist())) >= 2 and ref1[1][0] == 50
-    with _Knobs(few_max=8):
+    with knobs(few_max=8):
         _assert_few(_decode(dec, L3, S3, 50, ref3, "dvbs2 B=3"), 50, classes=2)
         _assert_few(_decode(dec, L1, S1, 50, ref1, "dvbs2 B=1"), 50, classes=2)
-        _lib.profile_enable(True)
-        _lib.profile_reset()
-        try:
+        with profiled():
             s3, i3, f3 = dec.decode_batch(L3, S3, 50)
             s1, i1, f1 = dec.decode(L1[0], S1[0], 50)
             n = _counters()
-        finally:
-            _lib.profile_enable(False)
         assert n["few_check"] == 2 * 52 * 2 and all(n[k] == 0 for k in FRAME_PARALLEL), n
     assert np.array_equal(s3, ref3[0]) and np.array_equal(i3, ref3[1])
     assert_bit_exact(f3, ref3[2])
@@ -198,13 +169,13 @@ def test_few_routing(gpu):
     dec = qamr.Decoder(case["vid"], case["cid"])
     L, S, ref = case["llr"], case["synd"], case["ref"][F.MI]
     first = lambda k: tuple(a[:k] for a in ref)  # noqa: E731
-    with _Knobs(few_max=4, resident=0):  # B above few_max: frame-parallel
+    with knobs(few_max=4, resident=0):  # B above few_max: frame-parallel
         _assert_frame_parallel(_decode(dec, L, S, F.MI, ref, "few_max=4 B=5"))
         _assert_few(_decode(dec, L[:4], S[:4], F.MI, first(4), "few_max=4 B=4"), F.MI)
-    with _Knobs(few_max=0, resident=0):  # off: every B
+    with knobs(few_max=0, resident=0):  # off: every B
         for B in (1, 5):
             _assert_frame_parallel(_decode(dec, L[:B], S[:B], F.MI, first(B), f"few_max=0 B={B}"))
-    with _Knobs(few_max=8, resident=1):  # a frame-resident code keeps k_resident
+    with knobs(few_max=8, resident=1):  # a frame-resident code keeps k_resident
         n = _decode(dec, L, S, F.MI, ref, "resident=1")
         _assert_frame_parallel(n)
         assert n["resident"] == 1 and n["check1"] == 0 and n["iter"] == 0, n
@@ -214,7 +185,7 @@ def test_few_routing(gpu):
     S17 = np.concatenate([S, np.zeros((S.shape[0], 1), np.uint8)], 1)
     dec17 = qamr.Decoder(vid17, cid17)
     assert dec17.max_check_degree == 17
-    with _Knobs(few_max=8, resident=0):
+    with knobs(few_max=8, resident=0):
         for B in (1, 5):
             r = orc17.decode_batch(L[:B], S17[:B], F.MI)
             _assert_frame_parallel(_decode(dec17, L[:B], S17[:B], F.MI, r, f"degree 17 B={B}"))
@@ -224,17 +195,15 @@ def test_few_max_survives_sizing(gpu):
     """The workspace size covers both routes: sized with the few-frame path off, the decode runs
     with it on (and the other way round) on that same workspace."""
     import qamr
-    from qamr import _lib
 
     case = F.mixed_case()
     dec = qamr.Decoder(case["vid"], case["cid"])
-    with _Knobs(few_max=0):
+    with knobs(few_max=0):
         need0 = dec.frames_workspace_bytes(5, F.MI)
-        _lib.tune_set("few_max", 8)
-        assert dec.frames_workspace_bytes(5, F.MI) == need0
-        n = _decode(dec, case["llr"], case["synd"], F.MI, case["ref"][F.MI], "sized off, run on")
-        _assert_few(n, F.MI, classes=len(F.MIXED_CLASSES))
-        _lib.tune_set("few_max", 0)
+        with knobs(few_max=8):
+            assert dec.frames_workspace_bytes(5, F.MI) == need0
+            n = _decode(dec, case["llr"], case["synd"], F.MI, case["ref"][F.MI], "sized off, run on")
+            _assert_few(n, F.MI, classes=len(F.MIXED_CLASSES))
         _assert_frame_parallel(_decode(dec, case["llr"], case["synd"], F.MI, case["ref"][F.MI], "sized on, run off"))
 
 
@@ -249,7 +218,7 @@ def test_few_decode_graph_capture(gpu):
     dec = qamr.Decoder(case["vid"], case["cid"])
     V = case["llr"].shape[1]
     to = lambda a: torch.from_numpy(np.array(a)).cuda()  # noqa: E731
-    with _Knobs(few_max=8):
+    with knobs(few_max=8):
         L, S = to(case["llr"][3:5]), to(case["synd"][3:5])
         fin = torch.full((3, V), F.PAD, dtype=torch.float64, device="cuda")
         succ = torch.zeros(2, dtype=torch.uint8, device="cuda")

@@ -5,7 +5,6 @@ noisemapper.pyx:27-63, 135-144, 295-307, 391-403, 563-620).  Every comparison is
 (conftest.assert_bit_exact: infinities compare as bits, NaN matches NaN), with both bodies of the
 grid index search (knob interp_fast 1 = coarse table + segment bisection, 0 = the reference's
 __binsearch probe for probe) and across coarse-table segment sizes (knob interp_seg)."""
-import contextlib
 import ctypes as C
 import hashlib
 import os
@@ -16,6 +15,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_bit_exact, golden
+
+from decode_fixture import knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -29,19 +30,6 @@ def fx():
     g = golden("interp.npz")
     assert int(g["n_cases"]) == N_CASES
     return g
-
-
-@contextlib.contextmanager
-def interp_fast(value):
-    from qamr import _lib
-
-    saved = _lib.tune_get("interp_fast")
-    try:
-        _lib.tune_set("interp_fast", value)
-        yield
-    finally:
-        _lib.tune_set("interp_fast", saved)
-    assert _lib.tune_get("interp_fast") == saved
 
 
 def make_nm(g, c):
@@ -106,7 +94,7 @@ def test_g_inv_vs_reference(gpu, fx, c, fast):
     n = fx["n300"]
     M = nm.order
     assert ref.shape == (M, n.size)
-    with interp_fast(fast):
+    with knobs(interp_fast=fast):
         got = nm.demap_noise(np.tile(n, M), np.repeat(np.arange(M, dtype=np.int64), n.size))
         assert_bit_exact(got.reshape(M, n.size), ref)
         for i in (0, M - 1):
@@ -131,7 +119,7 @@ def test_host_formulation1_vs_reference(gpu, fx, c, fast):
     k = f"c{c}_"
     n, j, ref = fx["n2000"], fx[k + "j2000"].astype(np.int64), fx[k + "la"]
     bps = nm.bit_per_symbol
-    with interp_fast(fast):
+    with knobs(interp_fast=fast):
         assert_bit_exact(nm.demap_lappr_simplified_array(n, j), ref)
         for s in (0, 7, 2001, 2006):
             assert_bit_exact(nm.demap_lappr_simplified(n[s], j[s]), ref[s * bps:(s + 1) * bps])
@@ -157,7 +145,7 @@ def test_device_block_vs_reference(gpu, fx, c):
     n_fi = to_dev(fx[k + "blk_n"], ld, torch.float64)
     j_fi = to_dev(fx[k + "blk_j"].astype(np.int64), ld, torch.int64)
     for fast in (1, 0):
-        with interp_fast(fast):
+        with knobs(interp_fast=fast):
             for alpha in (1.0, 0.7):
                 out = torch.full((S * bps, ld), float("nan"), dtype=torch.float64, device="cuda")
                 ret = nm.demap_simplified_device(n_fi, j_fi, B, alpha, out=out)
@@ -185,7 +173,6 @@ def test_segment_size_knob_is_result_invariant(gpu, fx, c):
     it changes): 2-entry segments, the default's neighbours, segments longer than the whole
     288-point grid of case 9 (one coarse entry) and the clamped ends give the reference's bits."""
     import torch
-    from qamr import _lib
 
     nm = make_nm(fx, c)
     k = f"c{c}_"
@@ -194,17 +181,12 @@ def test_segment_size_knob_is_result_invariant(gpu, fx, c):
     exp = block_expected(fx[k + "blk_la"], S, B, bps)
     n_fi = to_dev(fx[k + "blk_n"], ld, torch.float64)
     j_fi = to_dev(fx[k + "blk_j"].astype(np.int64), ld, torch.int64)
-    saved = _lib.tune_get("interp_seg")
-    assert saved == 4
-    try:
-        for seg in (1, 3, 6, 12, 0, 25):
-            _lib.tune_set("interp_seg", seg)
+    for seg in (1, 3, 6, 12, 0, 25):
+        with knobs(dict(interp_seg=4), interp_seg=seg):
             got = nm.demap_noise(np.tile(n300, M), np.repeat(np.arange(M, dtype=np.int64), n300.size))
             assert_bit_exact(got.reshape(M, n300.size), ginv)
             assert_bit_exact(nm.demap_simplified_device(n_fi, j_fi, B).cpu().numpy()[:, :B], exp)
             assert nm.grid_info() == (int(fx[k + "n_points"]), True)
-    finally:
-        _lib.tune_set("interp_seg", saved)
 
 
 # ------------------------------------------------------------------ properties
@@ -228,7 +210,7 @@ def test_device_kernel_matches_host_kernel(gpu, bps):
     n_fi, j_fi = to_dev(n, ld, torch.float64), to_dev(j, ld, torch.int64)
     res = []
     for fast in (1, 0):
-        with interp_fast(fast):
+        with knobs(interp_fast=fast):
             host = block_expected(nm.demap_lappr_simplified_array(n.ravel(), j.ravel()), S, B, bps)
             dev = nm.demap_simplified_device(n_fi, j_fi, B).cpu().numpy()[:, :B]
             assert_bit_exact(dev, host)

@@ -10,6 +10,7 @@ import pytest
 from conftest import assert_bit_exact, golden
 
 import oracle as O
+from decode_fixture import deal_sockets, knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -192,11 +193,7 @@ def _check_regular_irregular_var(N, dc, seed):
     """One check-degree class (dc) with variable degrees 1..5 and parallel edges: the codes the
     one-launch-per-iteration schedule (decode_small.hip k_iter) runs."""
     rng = np.random.default_rng(seed)
-    dv = rng.integers(1, 6, N)
-    sockets = np.repeat(np.arange(N), dv)
-    M = sockets.size // dc
-    sockets = sockets[rng.permutation(sockets.size)][:M * dc]
-    return sockets.astype(np.int64), np.repeat(np.arange(M), dc).astype(np.int64)
+    return deal_sockets(rng.integers(1, 6, N), dc, rng)
 
 
 @pytest.mark.parametrize("code", ["reg1008", "irr_d4", "irr_d7", "irr_d10", "reg_v1_d4", "reg_v2_d4"])
@@ -208,7 +205,7 @@ def test_fused_iteration_schedule_vs_oracle(gpu, code):
     frames that converge at iteration 0 (input already a codeword), +-inf / NaN / -0.0 LAPPRs."""
     import torch
     import qamr
-    from qamr import _lib, codes
+    from qamr import codes
 
     if code == "reg1008":
         vid, cid = codes.regular_code(1008)
@@ -232,31 +229,24 @@ def test_fused_iteration_schedule_vs_oracle(gpu, code):
     llr[9, 3] = -0.0
     L = torch.from_numpy(llr.T.copy()).cuda()
     S = torch.from_numpy(synd.T.copy()).cuda()
-    saved = {k: _lib.tune_get(k) for k in ("fused_iter", "iter_streams", "resident")}
-    try:
-        for mi in (1, 2, 3, 50):
-            outs = []
-            # one frame-resident launch per decode; one launch per iteration on two independent
-            # frame ranges / on one stream; then the three-launch flat schedule
-            for rs, fi, ns in ((1, 1, 2), (0, 1, 2), (0, 1, 1), (0, 0, 1)):
-                _lib.tune_set("resident", rs)
-                _lib.tune_set("fused_iter", fi)
-                _lib.tune_set("iter_streams", ns)
+    for mi in (1, 2, 3, 50):
+        outs = []
+        # one frame-resident launch per decode; one launch per iteration on two independent
+        # frame ranges / on one stream; then the three-launch flat schedule
+        for rs, fi, ns in ((1, 1, 2), (0, 1, 2), (0, 1, 1), (0, 0, 1)):
+            with knobs(resident=rs, fused_iter=fi, iter_streams=ns):
                 outs.append([x.clone() for x in dec.decode_device(L, S, B, mi)])
                 torch.cuda.synchronize()
-            (f0, s0, i0) = outs[-1]
-            for f1, s1, i1 in outs[:-1]:
-                assert torch.equal(s1, s0) and torch.equal(i1, i0), mi
-                assert torch.equal(f1[:, :B].view(torch.int64), f0[:, :B].view(torch.int64)), mi
-            f1, s1, i1 = outs[0]
-            s2, i2, fo = orc.decode_batch(llr, synd, mi)
-            assert np.array_equal(s1.cpu().numpy(), s2) and np.array_equal(i1.cpu().numpy(), i2), mi
-            assert_bit_exact(f1[:, :B].cpu().numpy().T, fo)
-            if mi == 50:
-                assert 0 < s2.sum() < B and (i2[:8] == 0).all() and s2[:8].all()
-    finally:
-        for k, v in saved.items():
-            _lib.tune_set(k, v)
+        (f0, s0, i0) = outs[-1]
+        for f1, s1, i1 in outs[:-1]:
+            assert torch.equal(s1, s0) and torch.equal(i1, i0), mi
+            assert torch.equal(f1[:, :B].view(torch.int64), f0[:, :B].view(torch.int64)), mi
+        f1, s1, i1 = outs[0]
+        s2, i2, fo = orc.decode_batch(llr, synd, mi)
+        assert np.array_equal(s1.cpu().numpy(), s2) and np.array_equal(i1.cpu().numpy(), i2), mi
+        assert_bit_exact(f1[:, :B].cpu().numpy().T, fo)
+        if mi == 50:
+            assert 0 < s2.sum() < B and (i2[:8] == 0).all() and s2[:8].all()
 
 
 @pytest.mark.parametrize("B", [1, 7, 65, 600])
@@ -267,7 +257,7 @@ def test_resident_batch_shapes_vs_oracle(gpu, B):
     padding columns of the output left untouched."""
     import torch
     import qamr
-    from qamr import _lib, codes
+    from qamr import codes
     from qamr.pipeline import leading_dim
 
     vid, cid = codes.regular_code(1008)
@@ -284,16 +274,12 @@ def test_resident_batch_shapes_vs_oracle(gpu, B):
     L[:, :B] = torch.from_numpy(llr.T.copy()).cuda()
     S = torch.zeros((dec.cnum, ld), dtype=torch.uint8, device="cuda")
     S[:, :B] = torch.from_numpy(synd.T.copy()).cuda()
-    saved = _lib.tune_get("resident")
-    try:
-        outs = []
-        for rs in (1, 0):
-            _lib.tune_set("resident", rs)
+    outs = []
+    for rs in (1, 0):
+        with knobs(resident=rs):
             fin = torch.full((V, ld), 7.0, dtype=torch.float64, device="cuda")
             outs.append([x.clone() for x in dec.decode_device(L, S, B, 30, final_fi=fin)])
             torch.cuda.synchronize()
-    finally:
-        _lib.tune_set("resident", saved)
     (f1, s1, i1), (f0, s0, i0) = outs
     assert torch.equal(s1, s0) and torch.equal(i1, i0)
     assert torch.equal(f1[:, :B].view(torch.int64), f0[:, :B].view(torch.int64))

@@ -21,6 +21,7 @@ import pytest
 from conftest import assert_bit_exact
 
 import oracle as O
+from decode_fixture import knobs, scattered_code
 
 pytestmark = pytest.mark.gpu
 
@@ -33,12 +34,7 @@ def _decoder(vid, cid):
 def _irregular_code(rng, C, degrees, V):
     """Checks with the given degree mix, sockets dealt at random over V variables
     (every variable used at least once)."""
-    deg = rng.choice(degrees, C)
-    E = int(deg.sum())
-    sockets = np.concatenate([np.arange(V), rng.integers(0, V, E - V)])
-    rng.shuffle(sockets)
-    cid = np.repeat(np.arange(C), deg)
-    return sockets.astype(np.int64), cid.astype(np.int64)
+    return scattered_code(rng, rng.choice(degrees, C), V)
 
 
 def test_irregular_degrees_vs_oracle(gpu):
@@ -88,23 +84,16 @@ def test_schedule_and_tuning_invariance(gpu):
     _, _, dec, pipe, batch, lappr = _dvbs2_batch(320, 3.6, seed=1)
     names = ["split", "check_ft", "check_per", "var_ft", "var_per", "nt", "lds_pad_kb", "compact", "side", "min_blocks",
              "split_min_blocks", "var_pace", "check_tail", "var_boost"]
-    saved = {k: _lib.tune_get(k) for k in names}
-    try:
-        ref = [x.clone() for x in dec.decode_device(lappr, batch.synd, batch.B, 50)]
-        torch.cuda.synchronize()
-        assert 0 < int(ref[1].sum()) < batch.B  # converging and failing frames
-        for t in TUNINGS:
-            for k, v in saved.items():
-                _lib.tune_set(k, v)
-            for k, v in t.items():
-                _lib.tune_set(k, v)
+    current = {k: _lib.tune_get(k) for k in names}   # every tuning sets all of them: its own values, else these
+    ref = [x.clone() for x in dec.decode_device(lappr, batch.synd, batch.B, 50)]
+    torch.cuda.synchronize()
+    assert 0 < int(ref[1].sum()) < batch.B  # converging and failing frames
+    for t in TUNINGS:
+        with knobs(**{**current, **t}):
             out = dec.decode_device(lappr, batch.synd, batch.B, 50)
             torch.cuda.synchronize()
-            assert torch.equal(out[1], ref[1]) and torch.equal(out[2], ref[2]), t
-            assert torch.equal(out[0][:, :batch.B].view(torch.int64), ref[0][:, :batch.B].view(torch.int64)), t
-    finally:
-        for k, v in saved.items():
-            _lib.tune_set(k, v)
+        assert torch.equal(out[1], ref[1]) and torch.equal(out[2], ref[2]), t
+        assert torch.equal(out[0][:, :batch.B].view(torch.int64), ref[0][:, :batch.B].view(torch.int64)), t
 
 
 def test_batch_composition_invariance_full_size(gpu):

@@ -25,17 +25,16 @@ import functools
 import numpy as np
 import pytest
 
-import oracle as O
-import test_gpu_repack_small_codes as R
-from test_gpu_degree_matrix import decode_and_compare, to_device
-from test_gpu_repack_small_codes import _predict, _running
+import decode_fixture as DF
+from decode_fixture import (LD, MI, NEVER, REPACK_DEFAULTS, REPACK_RUNS, assert_path, assert_repack_counts,
+                            decode_and_compare, deal_sockets, knobs, launches, oracle_of, predict_repack, profiled,
+                            to_device)
 
 pytestmark = pytest.mark.gpu
 
-MI = 30
 SPECIALS = np.array([-0.0, np.nan, np.inf, -np.inf])
 
-# knobs the schedules below touch, with their defaults (restored in a finally)
+# knobs the schedules below touch, with their defaults (every run sets all of them)
 DEFAULTS = dict(split=3, resident=1, fused_iter=1, iter_streams=2)
 # (label, knobs, path): default knobs, one launch per iteration (or the flat schedule where
 # iter_code refuses the code), lock-step frame-parallel
@@ -45,13 +44,11 @@ SCHEDULES = [("default", {}, "resident"),
 
 
 def dealt_code(dv, dc, rng):
-    """Variable v has dv[v] sockets; the sockets are shuffled and dealt dc per check (as
-    _check_regular_irregular_var of test_gpu_parity_edges.py, parallel edges kept)."""
+    """deal_sockets with no socket left over, so variable v has degree dv[v]; the last variable
+    has an edge (the reference sizes the code by max(e_to_v) + 1)."""
     dv = np.asarray(dv)
     assert dv.sum() % dc == 0 and dv[-1] >= 1
-    sockets = np.repeat(np.arange(dv.size), dv)
-    sockets = sockets[rng.permutation(sockets.size)]
-    vid, cid = sockets.astype(np.int64), np.repeat(np.arange(sockets.size // dc), dc).astype(np.int64)
+    vid, cid = deal_sockets(dv, dc, rng)
     assert np.array_equal(np.bincount(vid, minlength=dv.size), dv)
     return vid, cid
 
@@ -94,16 +91,6 @@ RESIDENT = {
 }
 
 
-def draw_frames(orc, rng, n, sigma):
-    """(llr, synd, word, sig) of n frames, drawn as _case of the repack file draws them."""
-    V = orc.vnum
-    word = rng.integers(0, 2, (n, V)).astype(np.uint8)
-    synd = np.stack([orc.eval_syndrome(w) for w in word])
-    sig = rng.uniform(*sigma, n)[:, None]
-    llr = 2 / sig ** 2 * ((1 - 2.0 * word) + sig * rng.standard_normal((n, V)))
-    return llr, synd, word, sig
-
-
 def plant_specials(orc, vid, llr, word, sig, lo, hi, mi):
     """In frames [lo, hi): make one frame an exact codeword, then put -0.0, NaN, inf, -inf on the
     first four isolated variables of that frame, of the first frame that iterates to the end and
@@ -141,24 +128,11 @@ def assert_planted_bits(fin, case, frames, iso):
     assert np.array_equal(got, want), (got, want)
 
 
-def oracle_of(case, mi):
-    if mi not in case["ref"]:
-        ref = case["orc"].decode_batch(case["llr"], case["synd"], mi)
-        for a in ref:
-            a.setflags(write=False)
-        case["ref"][mi] = ref
-    return case["ref"][mi]
-
-
 def make_case(vid, cid, n, sigma, seed, plant=()):
-    """n frames from default_rng(seed) and a cache of the oracle's decodes per max_iterations;
-    ``plant``: the (lo, hi) frame ranges that get special values on isolated variables."""
-    orc = O.OracleCode(vid, cid)
-    llr, synd, word, sig = draw_frames(orc, np.random.default_rng(seed), n, sigma)
-    planted = [plant_specials(orc, vid, llr, word, sig, lo, hi, MI) for lo, hi in plant]
-    llr.setflags(write=False)
-    synd.setflags(write=False)
-    return dict(vid=vid, cid=cid, orc=orc, llr=llr, synd=synd, ref={}, planted=planted)
+    """DF.make_case; ``plant``: the (lo, hi) frame ranges that get special values on isolated
+    variables (the case's ``planted``: one (frames, isolated variables) per range)."""
+    return DF.make_case(vid, cid, n, sigma, seed, lambda orc, llr, word, sig: [
+        plant_specials(orc, vid, llr, word, sig, lo, hi, MI) for lo, hi in plant])
 
 
 @functools.lru_cache(maxsize=None)
@@ -172,51 +146,28 @@ def resident_case(name):
     return case
 
 
-def launches(D):
-    from qamr import _lib
-
-    return {k: _lib.profile_query(f"{k}_d{D}")[1] for k in ("resident", "iter", "check", "check1")}
-
-
-def assert_path(path, mi, ld, n):
-    if path == "resident":
-        assert n == dict(resident=1, iter=0, check=0, check1=0), n
-    elif path == "iter":   # one chain of launches per stream: iter_streams = 2 ranges of 64-frame tiles
-        assert n == dict(resident=0, iter=(mi + 1) * min(2, ld // 64), check=0, check1=0), n
-    else:
-        assert path == "check"
-        assert n["check1"] > 0 and n["iter"] == 0 and n["resident"] == 0, n
-        assert n["check"] > 0 or mi == 1, n   # max_iterations = 1: the first sweep is the only one
+def iter_launches(mi, ld):
+    """One chain of iter_dD launches per stream: iter_streams = 2 ranges of 64-frame tiles."""
+    return (mi + 1) * min(2, ld // 64)
 
 
 def run_schedules(case, D, shapes, mis, schedules=SCHEDULES):
     """Every (B, ld) of shapes x max_iterations x schedule: equal to the oracle, on the path named."""
     import qamr
-    from qamr import _lib
 
-    for k, v in DEFAULTS.items():
-        assert _lib.tune_get(k) == v, f"default {k}={v} changed: update this test"
     dec = qamr.Decoder(case["vid"], case["cid"])
     assert dec.max_check_degree == D
-    try:
-        for B, ld in shapes:
-            L, S = to_device(case, B, ld)
-            for label, knobs, path in schedules:
-                for k, v in DEFAULTS.items():
-                    _lib.tune_set(k, knobs.get(k, v))
+    for B, ld in shapes:
+        L, S = to_device(case, B, ld)
+        for label, run, path in schedules:
+            with knobs(DEFAULTS, **run):
                 for mi in mis:
                     tag = (B, ld, label, mi)
-                    _lib.profile_enable(True)
-                    _lib.profile_reset()
-                    decode_and_compare(dec, L, S, B, mi, oracle_of(case, mi), tag)
-                    n = launches(D)
-                    _lib.profile_enable(False)
+                    with profiled():
+                        decode_and_compare(dec, L, S, B, mi, oracle_of(case, mi), tag)
+                        n = launches(D)
                     print(tag, n)
-                    assert_path(path, mi, ld, n)
-    finally:
-        _lib.profile_enable(False)
-        for k, v in DEFAULTS.items():
-            _lib.tune_set(k, v)
+                    assert_path(path, mi, n, iter_launches(mi, ld))
     return dec
 
 
@@ -247,23 +198,17 @@ def test_isolated_variables_keep_input_bits(gpu):
     output holds the input's bits (-0.0's sign, the NaN's payload, inf, -inf)."""
     import torch
     import qamr
-    from qamr import _lib
 
     case = resident_case("irr_c6_1100")
     assert_special_frames(case, MI)
     (frames, iso), = case["planted"]
     dec = qamr.Decoder(case["vid"], case["cid"])
     L, S = to_device(case, 96, 128)
-    try:
-        for label, knobs, _ in SCHEDULES:
-            for k, v in DEFAULTS.items():
-                _lib.tune_set(k, knobs.get(k, v))
+    for label, run, _ in SCHEDULES:
+        with knobs(DEFAULTS, **run):
             fin, _, _ = dec.decode_device(L, S, 96, MI)
             torch.cuda.synchronize()
-            assert_planted_bits(fin[:, :96].cpu().numpy().T, case, frames, iso)
-    finally:
-        for k, v in DEFAULTS.items():
-            _lib.tune_set(k, v)
+        assert_planted_bits(fin[:, :96].cpu().numpy().T, case, frames, iso)
 
 
 def test_resident_lds_boundary(gpu):
@@ -302,7 +247,6 @@ def test_max_var_degree_boundary(gpu, hub):
 
 
 # ------------------------------------------------- irregular variables under the column repack
-LD = 512
 REPACK = {"irr6": (6, 21, (0.5, 0.8)), "irr12": (12, 22, (0.35, 0.6))}   # check degree, seed, sigma
 
 
@@ -315,62 +259,41 @@ def repack_case(name):
 
 
 def assert_repack_inputs(name, case, B):
-    """The conditions of the repack file's _assert_inputs (which also asserts its own codes'
-    variable degree 3), from the graph and the oracle alone: one check degree, variable degrees
-    0..5 with 100..200 isolated; both ranges' running counts reach 80 % of their width, >= 5
-    distinct stops, both ranges are predicted to repack and end narrower than 256."""
-    H = LD // 2
+    """From the graph and the oracle alone: one check degree, variable degrees 0..5 with 100..200
+    isolated; then assert_repack_counts (both ranges' running counts reach 80 % of their width,
+    >= 5 distinct stops, both ranges are predicted to repack and end narrower than 256)."""
     assert np.array_equal(np.unique(np.bincount(case["cid"])), [REPACK[name][0]])
     deg = np.bincount(case["vid"], minlength=900)
     assert deg.size == 900 and deg.max() == 5 and 100 <= (deg == 0).sum() <= 200, np.bincount(deg)
-    succ, its, _ = oracle_of(case, MI)
-    counts = np.array([_running(succ, its, B, t) for t in range(MI - 1)])
-    assert (counts.min(axis=0) <= 0.8 * H).all(), counts.min(axis=0)
-    stops = np.unique(its[:B][succ[:B] != 0])
-    assert 0 < succ[:B].sum() and stops.size >= 5, stops
-    reps, widths = _predict(succ, its, B, MI)
-    assert min(reps) >= 1 and max(widths) < H, (reps, widths)
-    return reps, widths
+    return assert_repack_counts(case, B, MI)
 
 
 @pytest.mark.parametrize("name", list(REPACK))
 def test_irregular_var_repack_vs_oracle(gpu, name):
     """900 variables of degrees 0..5 (~ 150 isolated), dealt 6 and 12 per check, ld = 512 with
     split_min_blocks = 0: B = 512 and 450 at max_iterations = 30 under the knob sets of the repack
-    file's RUNS.  Every frame equals the oracle; with the default knobs the repack stats equal the
+    file's RUNS (REPACK_RUNS).  Every frame equals the oracle; with the default knobs the repack stats equal the
     prediction from the oracle's counts; with the repack or the lists off, and in lock-step,
     "never".  The planted frames (three kinds in each range) keep their special bits."""
     import qamr
-    from qamr import _lib
 
     case = repack_case(name)
     dc = REPACK[name][0]
     assert_special_frames(case, MI)
     want = {B: assert_repack_inputs(name, case, B) for B in (LD, 450)}
     ref = oracle_of(case, MI)
-    for k, v in R.DEFAULTS.items():
-        assert _lib.tune_get(k) == v, f"default {k}={v} changed: update this test"
     dec = qamr.Decoder(case["vid"], case["cid"])
-    try:
-        for B in (LD, 450):
-            L, S = to_device(case, B, LD)
-            for r, knobs in enumerate(R.RUNS):
-                for k, v in R.DEFAULTS.items():
-                    _lib.tune_set(k, {"resident": 0, **knobs}.get(k, v))
-                tag = (name, B, knobs)
-                _lib.profile_enable(True)
-                _lib.profile_reset()
+    for B in (LD, 450):
+        L, S = to_device(case, B, LD)
+        for r, run in enumerate(REPACK_RUNS):
+            tag = (name, B, run)
+            with knobs(REPACK_DEFAULTS, **{"resident": 0, **run}), profiled():
                 decode_and_compare(dec, L, S, B, MI, ref, tag)
                 n = launches(dc)
-                _lib.profile_enable(False)
                 stats = dec.repack_stats(LD, MI)
-                print(tag, n, "repack stats", stats, "predicted", want[B])
-                assert_path("iter" if r == 6 and dc == 6 else "check", MI, LD, n)
-                if r == 0:
-                    assert stats == want[B] == _predict(ref[0], ref[1], B, MI), (tag, stats, want[B])
-                elif r in (1, 4, 6):
-                    assert stats == R.NEVER, (tag, stats)
-    finally:
-        _lib.profile_enable(False)
-        for k, v in R.DEFAULTS.items():
-            _lib.tune_set(k, v)
+            print(tag, n, "repack stats", stats, "predicted", want[B])
+            assert_path("iter" if r == 6 and dc == 6 else "check", MI, n, iter_launches(MI, LD))
+            if r == 0:
+                assert stats == want[B] == predict_repack(ref[0], ref[1], B, MI), (tag, stats, want[B])
+            elif r in (1, 4, 6):
+                assert stats == NEVER, (tag, stats)

@@ -24,6 +24,7 @@ import pytest
 from conftest import assert_bit_exact, golden
 
 import oracle as O
+from decode_fixture import knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -148,18 +149,13 @@ def test_column_repack_vs_oracle(gpu, bps, snr, B, mi):
     # repacks at 50 % with a 1 024-workgroup grid
     runs = [dict(), dict(repack=0), dict(repack_grid=7), dict(repack_pct=50, repack_grid=1024)]
     names = ("repack", "repack_pct", "repack_grid")
-    saved = {k: _lib.tune_get(k) for k in names}
+    current = {k: _lib.tune_get(k) for k in names}   # every run sets all three: its own values, else these
     outs, stats = [], []
-    try:
-        for t in runs:
-            for k, v in saved.items():
-                _lib.tune_set(k, t.get(k, v))
+    for t in runs:
+        with knobs(**{**current, **t}):
             outs.append([x.clone() for x in pipe.decode(lappr, b)])
             torch.cuda.synchronize()
             stats.append(dec.repack_stats(pipe.ld, mi))
-    finally:
-        for k, v in saved.items():
-            _lib.tune_set(k, v)
     # the device repacked (no repack is decided before the last variable sweep: its transition
     # would end in the final parity sweep; with max_iterations 22 a 50 % threshold is first met there)
     (rep0, rep1), (w0, w1) = stats[0]

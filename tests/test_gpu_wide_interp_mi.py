@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_bit_exact, golden
-from test_gpu_interp import block_expected, interp_fast, sha, to_dev
+from decode_fixture import knobs
+from test_gpu_interp import block_expected, sha, to_dev
 from test_gpu_mi import run_device
 from test_gpu_mi import to_dev as mc_to_dev
 from test_gpu_mi_quad import ORDER21, ORDER30
@@ -96,7 +97,7 @@ def test_g_inv_and_formulation1_vs_reference(gpu, fx, k, fast):
     n109, ginv = fx[key + "n109"], fx[key + "ginv"]
     assert ginv.shape == (M, n109.size)
     n508, j508, la = fx[key + "n508"], fx[key + "j508"].astype(np.int64), fx[key + "la"]
-    with interp_fast(fast):
+    with knobs(interp_fast=fast):
         got = nm.demap_noise(np.tile(n109, M), np.repeat(np.arange(M, dtype=np.int64), n109.size))
         assert_bit_exact(got.reshape(M, n109.size), ginv)
         assert_bit_exact([nm.g_inv(n109[7], M - 1)], [ginv[M - 1, 7]])
@@ -122,7 +123,7 @@ def test_device_block_vs_reference(gpu, fx, k):
     n_fi = to_dev(fx[key + "blk_n"], ld, torch.float64)
     j_fi = to_dev(fx[key + "blk_j"].astype(np.int64), ld, torch.int64)
     for fast in (1, 0):
-        with interp_fast(fast):
+        with knobs(interp_fast=fast):
             for alpha in (1.0, 0.7):
                 out = torch.full((Sq * bps, ld), float("nan"), dtype=torch.float64, device="cuda")
                 ret = nm.demap_simplified_device(n_fi, j_fi, B, alpha, out=out)
@@ -183,7 +184,7 @@ def test_montecarlo_64pam_reference_search_and_which_masks(gpu, fx):
     pX = P_xhat(nm)
     x, y = mc_to_dev(fx[key + "x"].astype(np.int64), LD, torch.int64), mc_to_dev(fx[key + "y"], LD, torch.float64)
     exp_t, exp_i = expected_terms(fx, k), fx[key + "totals"].T
-    with interp_fast(0):
+    with knobs(interp_fast=0):
         info, terms = run_device(nm, pX, x, y, B, LD)
         assert_bit_exact(terms[:, :, :B], exp_t)
         assert_bit_exact(info[:, :B], exp_i)
@@ -308,7 +309,7 @@ def test_base_integral_64pam_with_reference_search(gpu, fx):
     from qamr.mutual_information import P_xhat, mutual_information_quad_batch
 
     pa, nm = make_nm(fx, 2)
-    with interp_fast(0):
+    with knobs(interp_fast=0):
         I, abserr, neval, ier = mutual_information_quad_batch("base", [nm], [P_xhat(nm)])
     eI, eabs, eneval, ewarned = expected(fx, 2, "base")
     assert_bit_exact([I[0], abserr[0]], [eI, eabs])
