@@ -164,18 +164,25 @@ QR_API int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, c
                    double *final_lappr, uint8_t *success, int32_t *iterations);
 
 /* --------------------------------------------- Decoder unit-test surface */
+/* Every *_host entry that takes n elements from host arrays follows one rule: a null handle is
+ * QR_EVALUE; n < 0 is QR_EVALUE ("negative size"); n == 0 is QR_OK with no device call; a null
+ * array with n > 0 is QR_EVALUE ("null pointer argument"). */
 /* Decoder.check_lappr (decoder.pyx:235-281): per-check satisfied flags
- * (check_ok[C]) and the whole-word flag, for one frame, computed on the GPU. */
+ * (check_ok[C]) and the whole-word flag, for one frame, computed on the GPU.  A null lappr or
+ * synd is QR_EVALUE (it used to be read); check_ok and all_ok may be null. */
 QR_API int qr_check_lappr_host(const qr_code *code, const double *lappr, const uint8_t *synd, uint8_t *check_ok,
                         uint8_t *all_ok);
-/* Decoder.check_synd_node / check_word (decoder.pyx:177-232) on a hard word. */
+/* Decoder.check_synd_node / check_word (decoder.pyx:177-232) on a hard word.  A null word or
+ * synd is QR_EVALUE (it used to be read). */
 QR_API int qr_check_word_host(const qr_code *code, const uint8_t *word, const uint8_t *synd, uint8_t *check_ok,
                        uint8_t *all_ok);
 /* Decoder.process_var_node (decoder.pyx:285-319) for a list of variable nodes:
- * updated[v] = lappr[v] + sum c2v[e]; v2c[e] = updated[v] - c2v[e]. */
+ * updated[v] = lappr[v] + sum c2v[e]; v2c[e] = updated[v] - c2v[e].  n_nodes < 0 is QR_EVALUE
+ * (it used to be QR_OK), and so is a null array with n_nodes > 0 (it used to be read). */
 QR_API int qr_process_var_nodes_host(const qr_code *code, const int64_t *nodes, int64_t n_nodes, const double *lappr,
                               const double *c2v, double *v2c, double *updated);
-/* Decoder.process_check_node (decoder.pyx:322-388) for a list of check nodes. */
+/* Decoder.process_check_node (decoder.pyx:322-388) for a list of check nodes.  n_nodes < 0 is
+ * QR_EVALUE (it used to be QR_OK), and so is a null array with n_nodes > 0 (it used to be read). */
 QR_API int qr_process_check_nodes_host(const qr_code *code, const int64_t *nodes, int64_t n_nodes, const uint8_t *synd,
                                 double *c2v, const double *v2c);
 
@@ -200,7 +207,8 @@ QR_API int qr_demap_tables(const qr_demap *dm, double *F_Y_thresholds, double *d
  * Out-of-range symbol indices yield NaN LAPPRs. */
 QR_API int qr_demap_batch_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, const double *d_n,
                           const int64_t *d_j, double alpha, double *d_lappr, void *stream);
-/* NoiseMapper.demap_lappr_array for one array from host memory: lappr[S*bps]. */
+/* NoiseMapper.demap_lappr_array for one array from host memory: lappr[S*bps].  S < 0 is QR_EVALUE
+ * (it used to be QR_OK), and so is a null array with S > 0 (it used to be read). */
 QR_API int qr_demap_host(const qr_demap *dm, int64_t S, const double *n, const int64_t *j, double *lappr);
 
 /* NoiseMapper.g_inv_search (noisemapper.pyx:310-345) over arrays, i.e.

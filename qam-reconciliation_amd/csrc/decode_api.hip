@@ -293,21 +293,25 @@ int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, const ui
 static int check_nodes_common(const qr_code *code, const void *vals, size_t val_bytes, const uint8_t *synd,
                               uint8_t *check_ok, uint8_t *all_ok, bool is_word) {
     if (!code) return set_error(QR_EVALUE, "null code");
-    DeviceGuard g(code->device);
-    std::lock_guard<std::mutex> lk(code->scratch.mu);
     const size_t C = code->C;
+    if (int rc = check_host_arrays((int64_t)C, vals, synd)) return rc;
+    HostTrip t(code->scratch, code->device);
     uint8_t *d_vals, *d_synd, *d_ok;
-    if (int rc = code->scratch.take(&d_vals, val_bytes, &d_synd, C, &d_ok, C)) return rc;
-    QR_HIP(hipMemcpy(d_vals, vals, val_bytes, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_synd, synd, C, hipMemcpyHostToDevice));
-    if (is_word)
-        k_check_word_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var, d_vals, d_synd, d_ok);
-    else
-        k_check_lappr_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var,
-                                                                   (const double *)d_vals, d_synd, d_ok);
-    QR_LAUNCH_CHECK();
+    if (!t.take(&d_vals, val_bytes, &d_synd, C, &d_ok, C)) return t.rc;
+    t.up(d_vals, (const uint8_t *)vals, val_bytes);
+    t.up(d_synd, synd, C);
+    if (t.ok()) {
+        if (is_word)
+            k_check_word_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var, d_vals, d_synd,
+                                                                      d_ok);
+        else
+            k_check_lappr_nodes<<<(unsigned)((C + 255) / 256), 256>>>(C, code->d_chk_ptr, code->d_chk_var,
+                                                                       (const double *)d_vals, d_synd, d_ok);
+        t.launched();
+    }
     std::vector<uint8_t> ok(C);
-    QR_HIP(hipMemcpy(ok.data(), d_ok, C, hipMemcpyDeviceToHost));
+    t.down(ok.data(), d_ok, C);
+    if (!t.ok()) return t.rc;
     uint8_t all = 1;
     for (size_t c = 0; c < C; ++c) {
         if (check_ok) check_ok[c] = ok[c];
@@ -332,50 +336,54 @@ int qr_check_word_host(const qr_code *code, const uint8_t *word, const uint8_t *
 int qr_process_var_nodes_host(const qr_code *code, const int64_t *nodes, int64_t n, const double *lappr,
                               const double *c2v, double *v2c, double *updated) {
     if (!code) return set_error(QR_EVALUE, "null code");
+    if (int rc = check_host_arrays(n, nodes, lappr, c2v, v2c, updated)) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (nodes[i] < 0 || nodes[i] >= code->V) return set_error(QR_EVALUE, "variable node index out of range");
-    if (n <= 0) return QR_OK;
-    DeviceGuard g(code->device);
-    std::lock_guard<std::mutex> lk(code->scratch.mu);
+    if (n == 0) return QR_OK;
+    HostTrip t(code->scratch, code->device);
     const size_t V = code->V, E = code->E;
     int64_t *d_nodes;
     double *d_lappr, *d_upd, *d_c2v, *d_v2c;
-    if (int rc = code->scratch.take(&d_nodes, n, &d_lappr, V, &d_upd, V, &d_c2v, E, &d_v2c, E)) return rc;
-    QR_HIP(hipMemcpy(d_nodes, nodes, n * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_lappr, lappr, V * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_upd, updated, V * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_c2v, c2v, E * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_v2c, v2c, E * 8, hipMemcpyHostToDevice));
-    k_var_nodes<<<(unsigned)((n + 255) / 256), 256>>>(d_nodes, n, code->d_var_ptr, code->d_var_edge, d_lappr, d_c2v,
-                                                      d_v2c, d_upd);
-    QR_LAUNCH_CHECK();
-    QR_HIP(hipMemcpy(v2c, d_v2c, E * 8, hipMemcpyDeviceToHost));
-    QR_HIP(hipMemcpy(updated, d_upd, V * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    if (!t.take(&d_nodes, (size_t)n, &d_lappr, V, &d_upd, V, &d_c2v, E, &d_v2c, E)) return t.rc;
+    t.up(d_nodes, nodes, n);
+    t.up(d_lappr, lappr, V);
+    t.up(d_upd, updated, V);
+    t.up(d_c2v, c2v, E);
+    t.up(d_v2c, v2c, E);
+    if (t.ok()) {
+        k_var_nodes<<<(unsigned)((n + 255) / 256), 256>>>(d_nodes, n, code->d_var_ptr, code->d_var_edge, d_lappr, d_c2v,
+                                                          d_v2c, d_upd);
+        t.launched();
+    }
+    t.down(v2c, d_v2c, E);
+    t.down(updated, d_upd, V);
+    return t.rc;
 }
 
 int qr_process_check_nodes_host(const qr_code *code, const int64_t *nodes, int64_t n, const uint8_t *synd,
                                 double *c2v, const double *v2c) {
     if (!code) return set_error(QR_EVALUE, "null code");
+    if (int rc = check_host_arrays(n, nodes, synd, c2v, v2c)) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (nodes[i] < 0 || nodes[i] >= code->C) return set_error(QR_EVALUE, "check node index out of range");
-    if (n <= 0) return QR_OK;
-    DeviceGuard g(code->device);
-    std::lock_guard<std::mutex> lk(code->scratch.mu);
+    if (n == 0) return QR_OK;
+    HostTrip t(code->scratch, code->device);
     const size_t C = code->C, E = code->E;
     int64_t *d_nodes;
     uint8_t *d_synd;
     double *d_c2v, *d_v2c;
-    if (int rc = code->scratch.take(&d_nodes, n, &d_synd, C, &d_c2v, E, &d_v2c, E)) return rc;
-    QR_HIP(hipMemcpy(d_nodes, nodes, n * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_synd, synd, C, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_c2v, c2v, E * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_v2c, v2c, E * 8, hipMemcpyHostToDevice));
-    k_check_nodes<<<(unsigned)((n + 255) / 256), 256>>>(d_nodes, n, code->d_chk_ptr, code->d_chk_edge, d_synd, d_c2v,
-                                                        d_v2c, code->d_gtab);
-    QR_LAUNCH_CHECK();
-    QR_HIP(hipMemcpy(c2v, d_c2v, E * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    if (!t.take(&d_nodes, (size_t)n, &d_synd, C, &d_c2v, E, &d_v2c, E)) return t.rc;
+    t.up(d_nodes, nodes, n);
+    t.up(d_synd, synd, C);
+    t.up(d_c2v, c2v, E);
+    t.up(d_v2c, v2c, E);
+    if (t.ok()) {
+        k_check_nodes<<<(unsigned)((n + 255) / 256), 256>>>(d_nodes, n, code->d_chk_ptr, code->d_chk_edge, d_synd, d_c2v,
+                                                            d_v2c, code->d_gtab);
+        t.launched();
+    }
+    t.down(c2v, d_c2v, E);
+    return t.rc;
 }
 
 }  // extern "C"

@@ -517,60 +517,60 @@ int qr_demap_batch_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, 
 // per symbol and the interleaved out[s*bps + k] layout of noisemapper.pyx:556.
 int qr_demap_host(const qr_demap *dm, int64_t S, const double *n, const int64_t *j, double *lappr) {
     if (!dm) return set_error(QR_EVALUE, "null demapper");
-    if (S <= 0) return QR_OK;
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
-    const int bps = dm->h.bps;
+    if (int rc = check_host_arrays(S, n, j, lappr)) return rc;
+    if (S == 0) return QR_OK;
+    HostTrip t(dm->scratch, dm->device);
+    const size_t bps = dm->h.bps;
     double *d_n, *d_l;
     int64_t *d_j;
-    if (int rc = dm->scratch.take(&d_n, (size_t)S, &d_j, (size_t)S, &d_l, (size_t)S * bps)) return rc;
-    QR_HIP(hipMemcpy(d_n, n, S * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_j, j, S * 8, hipMemcpyHostToDevice));
+    if (!t.take(&d_n, (size_t)S, &d_j, (size_t)S, &d_l, S * bps)) return t.rc;
+    t.up(d_n, n, S);
+    t.up(d_j, j, S);
     // ld = 1, B = 1: item = s, f = 0; lappr index (s*bps + k) * 1 + 0 = interleaved output.
-    {
+    if (t.ok()) {
         ProfScope ps("demap", nullptr);
         launch_demap_bps(dm->h.bps, g_demap_fast.load() != 0, (unsigned)((S + 255) / 256), nullptr, dm, 1, 1, S, d_n,
                          d_j, 1.0, d_l);
-        QR_LAUNCH_CHECK();
+        t.launched();
     }
-    QR_HIP(hipMemcpy(lappr, d_l, S * bps * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    t.down(lappr, d_l, S * bps);
+    return t.rc;
 }
 
 int qr_g_inv_search_host(const qr_demap *dm, int64_t n, const double *n_hat, const int64_t *i, double y_accuracy,
                          double *y_hat) {
     if (!dm) return set_error(QR_EVALUE, "null demapper");
-    if (n < 0) return set_error(QR_EVALUE, "negative size");
+    if (int rc = check_host_arrays(n, n_hat, i, y_hat)) return rc;
     if (n == 0) return QR_OK;
-    if (!n_hat || !i || !y_hat) return set_error(QR_EVALUE, "null pointer argument");
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    HostTrip t(dm->scratch, dm->device);
     double *d_n, *d_y;
     int64_t *d_i;
-    if (int rc = dm->scratch.take(&d_n, (size_t)n, &d_i, (size_t)n, &d_y, (size_t)n)) return rc;
-    QR_HIP(hipMemcpy(d_n, n_hat, (size_t)n * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_i, i, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_g_inv_search<<<(unsigned)((n + 255) / 256), 256>>>(dm->d_tables, dm->d_mtab, n, d_n, d_i, y_accuracy,
-                                                         g_demap_fast.load() != 0, d_y);
-    QR_LAUNCH_CHECK();
-    QR_HIP(hipMemcpy(y_hat, d_y, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    if (!t.take(&d_n, (size_t)n, &d_i, (size_t)n, &d_y, (size_t)n)) return t.rc;
+    t.up(d_n, n_hat, n);
+    t.up(d_i, i, n);
+    if (t.ok()) {
+        k_g_inv_search<<<(unsigned)((n + 255) / 256), 256>>>(dm->d_tables, dm->d_mtab, n, d_n, d_i, y_accuracy,
+                                                             g_demap_fast.load() != 0, d_y);
+        t.launched();
+    }
+    t.down(y_hat, d_y, n);
+    return t.rc;
 }
 
 int qr_F_Y_host(const qr_demap *dm, int64_t n, const double *y, double *F) {
     if (!dm) return set_error(QR_EVALUE, "null demapper");
-    if (n < 0) return set_error(QR_EVALUE, "negative size");
+    if (int rc = check_host_arrays(n, y, F)) return rc;
     if (n == 0) return QR_OK;
-    if (!y || !F) return set_error(QR_EVALUE, "null pointer argument");
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    HostTrip t(dm->scratch, dm->device);
     double *d_y, *d_F;
-    if (int rc = dm->scratch.take(&d_y, (size_t)n, &d_F, (size_t)n)) return rc;
-    QR_HIP(hipMemcpy(d_y, y, (size_t)n * 8, hipMemcpyHostToDevice));
-    k_public_F_Y<<<(unsigned)((n + 255) / 256), 256>>>(dm->d_tables, n, d_y, d_F);
-    QR_LAUNCH_CHECK();
-    QR_HIP(hipMemcpy(F, d_F, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    if (!t.take(&d_y, (size_t)n, &d_F, (size_t)n)) return t.rc;
+    t.up(d_y, y, n);
+    if (t.ok()) {
+        k_public_F_Y<<<(unsigned)((n + 255) / 256), 256>>>(dm->d_tables, n, d_y, d_F);
+        t.launched();
+    }
+    t.down(F, d_F, n);
+    return t.rc;
 }
 
 int qr_bob_map_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, const double *d_y, int64_t *d_xhat,

@@ -221,49 +221,47 @@ int qr_demap_grid_host(const qr_demap *dm, double *y, double *F) {
 int qr_g_inv_host(const qr_demap *dm, int64_t n, const double *n_hat, const int64_t *i, double *y_hat) {
     if (!dm) return set_error(QR_EVALUE, "null demapper");
     if (int rc = need_grid(dm)) return rc;
-    if (n < 0) return set_error(QR_EVALUE, "negative size");
+    if (int rc = check_host_arrays(n, n_hat, i, y_hat)) return rc;
     if (n == 0) return QR_OK;
-    if (!n_hat || !i || !y_hat) return set_error(QR_EVALUE, "null pointer argument");
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    HostTrip t(dm->scratch, dm->device);
     double *d_n, *d_y;
     int64_t *d_i;
-    if (int rc = dm->scratch.take(&d_n, (size_t)n, &d_i, (size_t)n, &d_y, (size_t)n)) return rc;
-    QR_HIP(hipMemcpy(d_n, n_hat, (size_t)n * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_i, i, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (!t.take(&d_n, (size_t)n, &d_i, (size_t)n, &d_y, (size_t)n)) return t.rc;
+    t.up(d_n, n_hat, n);
+    t.up(d_i, i, n);
     const GridView gv = grid_view(dm);
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (grid_fast(dm)) k_g_inv_interp<true><<<grid, 256>>>(dm->d_tables, gv, n, d_n, d_i, d_y);
-    else k_g_inv_interp<false><<<grid, 256>>>(dm->d_tables, gv, n, d_n, d_i, d_y);
-    QR_LAUNCH_CHECK();
-    QR_HIP(hipMemcpy(y_hat, d_y, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    if (t.ok()) {
+        if (grid_fast(dm)) k_g_inv_interp<true><<<grid, 256>>>(dm->d_tables, gv, n, d_n, d_i, d_y);
+        else k_g_inv_interp<false><<<grid, 256>>>(dm->d_tables, gv, n, d_n, d_i, d_y);
+        t.launched();
+    }
+    t.down(y_hat, d_y, n);
+    return t.rc;
 }
 
 int qr_demap_simplified_host(const qr_demap *dm, int64_t S, const double *n, const int64_t *j, double *lappr) {
     if (!dm) return set_error(QR_EVALUE, "null demapper");
     if (int rc = need_grid(dm)) return rc;
-    if (S < 0) return set_error(QR_EVALUE, "negative size");
+    if (int rc = check_host_arrays(S, n, j, lappr)) return rc;
     if (S == 0) return QR_OK;
-    if (!n || !j || !lappr) return set_error(QR_EVALUE, "null pointer argument");
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
-    const int bps = dm->h.bps;
+    HostTrip t(dm->scratch, dm->device);
+    const size_t bps = dm->h.bps;
     double *d_n, *d_l;
     int64_t *d_j;
-    if (int rc = dm->scratch.take(&d_n, (size_t)S, &d_j, (size_t)S, &d_l, (size_t)S * bps)) return rc;
-    QR_HIP(hipMemcpy(d_n, n, (size_t)S * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_j, j, (size_t)S * 8, hipMemcpyHostToDevice));
+    if (!t.take(&d_n, (size_t)S, &d_j, (size_t)S, &d_l, S * bps)) return t.rc;
+    t.up(d_n, n, S);
+    t.up(d_j, j, S);
     const GridView gv = grid_view(dm);
     const unsigned grid = (unsigned)((S + 255) / 256);
-    {
+    if (t.ok()) {
         ProfScope ps("demap_interp", nullptr);
         if (grid_fast(dm)) k_demap_interp_lane<true><<<grid, 256>>>(dm->d_tables, gv, S, d_n, d_j, d_l);
         else k_demap_interp_lane<false><<<grid, 256>>>(dm->d_tables, gv, S, d_n, d_j, d_l);
-        QR_LAUNCH_CHECK();
+        t.launched();
     }
-    QR_HIP(hipMemcpy(lappr, d_l, (size_t)S * bps * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    t.down(lappr, d_l, S * bps);
+    return t.rc;
 }
 
 int qr_demap_simplified_batch_device(const qr_demap *dm, int32_t B, int32_t ld, int64_t S, const double *n,

@@ -416,19 +416,18 @@ int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x, const
         return set_error(QR_EUNSUPPORTED, "the estimator serves bit_per_symbol <= %d (got %d)", kDemapWaveMaxBps, dm->h.bps);
     const unsigned mask = which ? (which[0] ? kMiXXhat : 0u) | (which[1] ? kMiXY : 0u) | (which[2] ? kMiXNXhat : 0u) : kMiAll;
     const int ld = (int)align_up((size_t)N, kWave);
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    HostTrip t(dm->scratch, dm->device);
     int64_t *d_x;
     double *d_y, *d_t;
-    if (int rc = dm->scratch.take(&d_x, (size_t)ld, &d_y, (size_t)ld, &d_t, (size_t)3 * ld)) return rc;
-    QR_HIP(hipMemcpy(d_x, x, (size_t)N * 8, hipMemcpyHostToDevice));
-    QR_HIP(hipMemcpy(d_y, y, (size_t)N * 8, hipMemcpyHostToDevice));
-    if (int rc = mi_launch(dm, mask, (int)N, ld, 1, d_x, d_y, nullptr, d_t, nullptr)) return rc;
+    if (!t.take(&d_x, (size_t)ld, &d_y, (size_t)ld, &d_t, (size_t)3 * ld)) return t.rc;
+    t.up(d_x, x, N);
+    t.up(d_y, y, N);
+    if (t.ok()) t.rc = mi_launch(dm, mask, (int)N, ld, 1, d_x, d_y, nullptr, d_t, nullptr);
     std::vector<double> h((size_t)N);
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < 3 && t.ok(); ++q) {
         double acc = 0.0;
         if ((mask >> q) & 1u) {
-            QR_HIP(hipMemcpy(h.data(), d_t + (size_t)q * ld, (size_t)N * 8, hipMemcpyDeviceToHost));
+            t.down(h.data(), d_t + (size_t)q * ld, N);
             for (int64_t p = 0; p < N; ++p) acc = q == 2 ? acc - h[(size_t)p] : acc + h[(size_t)p];
         } else {
             std::fill(h.begin(), h.end(), 0.0);
@@ -436,7 +435,7 @@ int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x, const
         if (terms) memcpy(terms + (size_t)q * N, h.data(), (size_t)N * 8);
         out[q] = acc / (double)N;
     }
-    return QR_OK;
+    return t.rc;
 }
 
 int qr_log2_host(int64_t n, const double *x, double *out) {
@@ -475,16 +474,15 @@ int qr_mi_integrand_host(const qr_demap *dm, int32_t kind, int64_t n, const doub
     if (n < 0) return set_error(QR_EVALUE, "negative size");
     if (kind == kMiQuadBase && !dm->d_mi)
         return set_error(QR_EVALUE, "the mutual-information tables have not been created (qr_demap_mi_tables)");
+    if (int rc = check_host_arrays(n, x, f)) return rc;
     if (n == 0) return QR_OK;
-    if (!x || !f) return set_error(QR_EVALUE, "null pointer argument");
-    DeviceGuard g(dm->device);
-    std::lock_guard<std::mutex> lk(dm->scratch.mu);
+    HostTrip t(dm->scratch, dm->device);
     double *d_x, *d_f;
-    if (int rc = dm->scratch.take(&d_x, (size_t)n, &d_f, (size_t)n)) return rc;
-    QR_HIP(hipMemcpy(d_x, x, (size_t)n * 8, hipMemcpyHostToDevice));
-    if (int rc = mi_integrand_launch(dm, kind, n, d_x, d_f, nullptr)) return rc;
-    QR_HIP(hipMemcpy(f, d_f, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return QR_OK;
+    if (!t.take(&d_x, (size_t)n, &d_f, (size_t)n)) return t.rc;
+    t.up(d_x, x, n);
+    if (t.ok()) t.rc = mi_integrand_launch(dm, kind, n, d_x, d_f, nullptr);
+    t.down(f, d_f, n);
+    return t.rc;
 }
 
 int qr_mi_quad_batch(const qr_demap *const *dms, const double *p_xhat, const uint8_t *sign_cfg, int32_t P, int32_t kind,

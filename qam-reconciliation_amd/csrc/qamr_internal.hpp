@@ -136,6 +136,45 @@ struct DeviceGuard {
     int prev_ = 0, dev_ = 0;
 };
 
+// The argument rule of every *_host entry that takes n elements from host arrays: a negative n and,
+// with n > 0, a null array are QR_EVALUE (n == 0 is the caller's early QR_OK, before any device call).
+template <typename... P>
+inline int check_host_arrays(int64_t n, const P *...arrays) {
+    if (n < 0) return set_error(QR_EVALUE, "negative size");
+    if (n > 0 && (... || !arrays)) return set_error(QR_EVALUE, "null pointer argument");
+    return QR_OK;
+}
+
+// One round trip of host arrays through a handle's scratch.  It holds the device and the scratch's
+// lock for its lifetime; an entry reads: validate, take, up, launch, down, return rc.  The first
+// failure stays in rc and turns the later copies into no-ops; byte counts are formed here, in size_t.
+struct HostTrip {
+    HostTrip(Scratch &s, int device) : g_(device), lk_(s.mu), scratch_(s) {}
+    template <typename... A>
+    bool take(A... regions) {  // Scratch::take; false (and rc) when the scratch cannot grow
+        rc = scratch_.take(regions...);
+        return rc == QR_OK;
+    }
+    template <typename T>
+    void up(T *dev, const T *host, size_t n) { copy(dev, host, n * sizeof(T), hipMemcpyHostToDevice); }
+    template <typename T>
+    void down(T *host, const T *dev, size_t n) { copy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost); }
+    bool ok() const { return rc == QR_OK; }  // launch only then: a failed upload left the inputs unset
+    void launched() { fail(hipGetLastError(), "launch"); }
+    int rc = QR_OK;
+
+  private:
+    void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        if (rc == QR_OK) fail(hipMemcpy(dst, src, bytes, kind), "hipMemcpy");
+    }
+    void fail(hipError_t e, const char *what) {
+        if (e != hipSuccess) rc = hip_fail(e, what, __FILE__, __LINE__);
+    }
+    DeviceGuard g_;
+    std::lock_guard<std::mutex> lk_;
+    Scratch &scratch_;
+};
+
 // Diagnostic twin only (libqamr_clock.so, QR_EXPERIMENT_CLOCK=1; the product library carries no
 // stamp): a workgroup's shader-clock (s_memtime) and 100 MHz realtime (s_memrealtime) spans added
 // to acc[0..2] = {cycles, ticks, workgroups} by thread 0 (vector atomics) when the scope ends, and

@@ -164,8 +164,61 @@ def require_gpu():
         raise QamrError("no HIP device visible: qamr runs only on the GPU (no CPU fallback)")
 
 
+# ------------------------------------------------- Python objects -> C arguments
 def ptr(a: np.ndarray):
     return C.c_void_p(a.ctypes.data)
+
+
+def dptr(t):
+    """A device tensor's address (None stays None, the C-ABI's null)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_arg(stream, device):
+    """(stream, its C argument); torch's current stream of `device` when none is given."""
+    if stream is None:
+        import torch
+
+        stream = torch.cuda.current_stream(device)
+    return stream, C.c_void_p(stream.cuda_stream)
+
+
+C_NAMES = {np.dtype(np.float64): "double", np.dtype(np.int64): "long", np.dtype(np.uint8): "unsigned char"}
+
+
+def bool_as_u8(a):
+    """np.asarray(a), a bool array viewed as unsigned char (Cython takes either for `unsigned char[:]`)."""
+    arr = np.asarray(a)
+    return arr.view(np.uint8) if arr.dtype == np.bool_ else arr
+
+
+def as_buffer(a, dtype, *, name=None, flat=False):
+    """Cython typed-memoryview semantics: the exact dtype (bool viewed as unsigned char), contiguous;
+    flat=True ravels (noisemapper.pyx's np.ndarray arguments), otherwise 1-D is required (decoder.pxd)."""
+    arr = bool_as_u8(a) if dtype == np.uint8 else np.asarray(a)
+    suffix = f" ({name})" if name else ""
+    if arr.dtype != dtype:
+        raise ValueError(f"Buffer dtype mismatch, expected '{C_NAMES[np.dtype(dtype)]}' but got '{arr.dtype}'{suffix}")
+    if flat:
+        arr = arr.ravel()
+    elif arr.ndim != 1:
+        raise ValueError(f"Buffer has wrong number of dimensions (expected 1, got {arr.ndim}){suffix}")
+    return np.ascontiguousarray(arr)
+
+
+def check_2d(t, what, name, dims):
+    """`t` is a rank-2 torch tensor (of any placement): its shape."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError(f"{what}: {name} must be a 2-D tensor {dims}")
+    return t.shape
+
+
+def check_batch(B, ld, what):
+    """The frame-innermost batch shape every *_device kernel assumes."""
+    if ld % 64 or not 0 < int(B) <= ld:
+        raise ValueError(f"{what}: need ld % 64 == 0 and 0 < B <= ld (B={B}, ld={ld})")
 
 
 # ------------------------------------------------------------------ tuning

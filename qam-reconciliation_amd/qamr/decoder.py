@@ -22,38 +22,30 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import as_buffer, bool_as_u8, check, check_2d, check_batch, check_tensor, dptr, ptr, stream_arg
 
 
-def _as_buffer(a, dtype, name, expected):
-    """Cython typed-memoryview semantics: exact dtype, 1-D (decoder.pxd)."""
-    arr = np.asarray(a)
-    if arr.dtype == np.bool_ and dtype == np.uint8:
-        arr = arr.view(np.uint8)
-    if arr.dtype != dtype:
-        raise ValueError(f"Buffer dtype mismatch, expected '{expected}' but got '{arr.dtype}' ({name})")
-    if arr.ndim != 1:
-        raise ValueError(f"Buffer has wrong number of dimensions (expected 1, got {arr.ndim}) ({name})")
-    return np.ascontiguousarray(arr)
-
-
-def _as_inout(a, dtype, name, expected):
+def _as_inout(a, dtype, name):
     """In/out buffers must be written in place: exact dtype, 1-D, contiguous."""
     if not isinstance(a, np.ndarray):
         raise ValueError(f"{name} must be a numpy array (written in place)")
-    if a.dtype != dtype:
-        raise ValueError(f"Buffer dtype mismatch, expected '{expected}' but got '{a.dtype}' ({name})")
+    as_buffer(a, dtype, name=name, flat=True)   # the dtype rule and its message; the array itself is used
     if a.ndim != 1 or not a.flags.c_contiguous or not a.flags.writeable:
         raise ValueError(f"{name} must be a writeable 1-D C-contiguous array")
     return a
+
+
+def _stream_key(stream) -> int:
+    """The stream's handle as an integer (0 = the default stream)."""
+    return stream_arg(stream, None)[1].value or 0
 
 
 class Decoder:
     """``Decoder(e_to_v, e_to_c)`` -- Tanner graph given as an edge list."""
 
     def __init__(self, e_to_v, e_to_c, device: int = 0):
-        vid = _as_buffer(e_to_v, np.int64, "e_to_v", "long")
-        cid = _as_buffer(e_to_c, np.int64, "e_to_c", "long")
+        vid = as_buffer(e_to_v, np.int64, name="e_to_v")
+        cid = as_buffer(e_to_c, np.int64, name="e_to_c")
         L = _lib.load()
         h = C.c_void_p()
         check(L.qr_code_create(ptr(vid), ptr(cid), vid.size, cid.size, int(device), C.byref(h)), "Decoder")
@@ -97,48 +89,41 @@ class Decoder:
         return self._device
 
     # ------------------------------------------------------ syndrome checks
-    def _check_word_flags(self, word, synd):
-        w = _as_buffer(word, np.uint8, "word", "unsigned char")
-        s = _as_buffer(synd, np.uint8, "synd", "unsigned char")
-        if w.size != self._V:
-            raise ValueError("Size of word does not match number of vnodes")
+    def _check_nodes(self, values, synd, lappr: bool):
+        """Every check against a hard word, or against sign(lappr): (flags uint8 [C], all satisfied)."""
+        name = "lappr" if lappr else "word"
+        v = as_buffer(values, np.float64 if lappr else np.uint8, name=name)
+        s = as_buffer(synd, np.uint8, name="synd")
+        if v.size != self._V:
+            raise ValueError(f"Size of {name} does not match number of vnodes")
         if s.size != self._C:
             raise ValueError("Size of synd does not match number of cnodes")
         flags = np.empty(self._C, np.uint8)
         allok = C.c_uint8()
-        check(_lib.load().qr_check_word_host(self._h, ptr(w), ptr(s), ptr(flags), C.byref(allok)), "check_word")
+        L = _lib.load()
+        entry = L.qr_check_lappr_host if lappr else L.qr_check_word_host
+        check(entry(self._h, ptr(v), ptr(s), ptr(flags), C.byref(allok)), f"check_{name}")
         return flags, int(allok.value)
 
     def check_synd_node(self, check_node_index, word, synd):
         """decoder.pyx:190-209: ``parity ^ 1`` of one check for a hard word."""
-        flags, _ = self._check_word_flags(word, synd)
-        return int(flags[int(check_node_index)])
+        return int(self._check_nodes(word, synd, False)[0][int(check_node_index)])
 
     def check_word(self, word, synd):
         """decoder.pyx:220-232: 1 iff every check is satisfied by the hard word."""
-        _, allok = self._check_word_flags(word, synd)
-        return allok
+        return self._check_nodes(word, synd, False)[1]
 
     def check_lappr(self, lappr, synd):
         """decoder.pyx:260-281: 1 iff sign(lappr) (< 0 -> bit 1) satisfies synd."""
-        l = _as_buffer(lappr, np.float64, "lappr", "double")
-        s = _as_buffer(synd, np.uint8, "synd", "unsigned char")
-        if l.size != self._V:
-            raise ValueError("Size of lappr does not match number of vnodes")
-        if s.size != self._C:
-            raise ValueError("Size of synd does not match number of cnodes")
-        flags = np.empty(self._C, np.uint8)
-        allok = C.c_uint8()
-        check(_lib.load().qr_check_lappr_host(self._h, ptr(l), ptr(s), ptr(flags), C.byref(allok)), "check_lappr")
-        return int(allok.value)
+        return self._check_nodes(lappr, synd, True)[1]
 
     # ------------------------------------------------------ node processing
     def process_var_node(self, node_index, lappr_data, check_to_var, var_to_check, updated_lappr):
         """decoder.pyx:301-319 (writes var_to_check and updated_lappr in place)."""
-        l = _as_buffer(lappr_data, np.float64, "lappr_data", "double")
-        c2v = _as_buffer(check_to_var, np.float64, "check_to_var", "double")
-        v2c = _as_inout(var_to_check, np.float64, "var_to_check", "double")
-        upd = _as_inout(updated_lappr, np.float64, "updated_lappr", "double")
+        l = as_buffer(lappr_data, np.float64, name="lappr_data")
+        c2v = as_buffer(check_to_var, np.float64, name="check_to_var")
+        v2c = _as_inout(var_to_check, np.float64, "var_to_check")
+        upd = _as_inout(updated_lappr, np.float64, "updated_lappr")
         if l.size < self._V or upd.size < self._V or c2v.size < self._E or v2c.size < self._E:
             raise ValueError("message/LAPPR arrays are shorter than the graph")
         nodes = np.array([int(node_index)], np.int64)
@@ -147,9 +132,9 @@ class Decoder:
 
     def process_check_node(self, node_index, synd, check_to_var, var_to_check):
         """decoder.pyx:372-388 (writes check_to_var in place); returns 0."""
-        s = _as_buffer(synd, np.uint8, "synd", "unsigned char")
-        c2v = _as_inout(check_to_var, np.float64, "check_to_var", "double")
-        v2c = _as_buffer(var_to_check, np.float64, "var_to_check", "double")
+        s = as_buffer(synd, np.uint8, name="synd")
+        c2v = _as_inout(check_to_var, np.float64, "check_to_var")
+        v2c = as_buffer(var_to_check, np.float64, name="var_to_check")
         if s.size < self._C or c2v.size < self._E or v2c.size < self._E:
             raise ValueError("message/syndrome arrays are shorter than the graph")
         nodes = np.array([int(node_index)], np.int64)
@@ -160,8 +145,8 @@ class Decoder:
     # ---------------------------------------------------------------- decode
     def decode(self, lappr_data, synd, max_iterations):
         """decoder.pyx:441-455 -> (success, iterations, final_lappr)."""
-        l = _as_buffer(lappr_data, np.float64, "lappr_data", "double")
-        s = _as_buffer(synd, np.uint8, "synd", "unsigned char")
+        l = as_buffer(lappr_data, np.float64, name="lappr_data")
+        s = as_buffer(synd, np.uint8, name="synd")
         if l.size != self._V:
             raise ValueError(f"lappr has {l.size} entries, the code has {self._V} variable nodes")
         if s.size != self._C:
@@ -175,10 +160,7 @@ class Decoder:
         lappr: float64 [B, V]; synd: uint8/bool [B, C].
         Returns (success uint8[B], iterations int32[B], final float64[B, V])."""
         l = np.ascontiguousarray(lappr)
-        s = np.asarray(synd)
-        if s.dtype == np.bool_:
-            s = s.view(np.uint8)
-        s = np.ascontiguousarray(s)
+        s = np.ascontiguousarray(bool_as_u8(synd))
         if l.dtype != np.float64 or s.dtype != np.uint8:
             raise ValueError("decode_batch expects float64 LAPPRs and uint8 syndromes")
         if l.ndim != 2 or s.ndim != 2 or l.shape[0] != s.shape[0]:
@@ -210,39 +192,38 @@ class Decoder:
         workspace is kept per stream, so calls on different streams never share it."""
         import torch
 
-        from ._lib import check_tensor
-
-        dev = self._device
-        if not isinstance(lappr_fi, torch.Tensor) or lappr_fi.dim() != 2:
-            raise ValueError("decode_device: lappr_fi must be a 2-D tensor [V, ld]")
-        V, ld = lappr_fi.shape
+        V, ld = check_2d(lappr_fi, "decode_device", "lappr_fi", "[V, ld]")
         if V != self._V:
             raise ValueError("decode_device: tensor shapes do not match the code")
-        if ld % 64 or not 0 < int(B) <= ld:
-            raise ValueError(f"decode_device: need ld % 64 == 0 and 0 < B <= ld (B={B}, ld={ld})")
-        check_tensor(lappr_fi, "lappr_fi", (self._V, ld), torch.float64, dev)
-        check_tensor(synd_fi, "synd_fi", (self._C, ld), torch.uint8, dev)
-        tdev = lappr_fi.device
-        if final_fi is None:
-            final_fi = torch.empty_like(lappr_fi)
-        if success is None:
-            success = torch.empty(B, dtype=torch.uint8, device=tdev)
-        if iters is None:
-            iters = torch.empty(B, dtype=torch.int32, device=tdev)
-        check_tensor(final_fi, "final_fi", (self._V, ld), torch.float64, dev)
-        if success.numel() < B or iters.numel() < B:
-            raise ValueError(f"decode_device: success/iters must hold at least B={B} entries")
-        check_tensor(success, "success", (success.numel(),), torch.uint8, dev)
-        check_tensor(iters, "iters", (iters.numel(),), torch.int32, dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(tdev)
+        check_batch(B, ld, "decode_device")
+        check_tensor(lappr_fi, "lappr_fi", (self._V, ld), torch.float64, self._device)
+        check_tensor(synd_fi, "synd_fi", (self._C, ld), torch.uint8, self._device)
+        final_fi, success, iters = self._outputs("decode_device", B, lappr_fi, final_fi, "final_fi", (self._V, ld),
+                                                 success, iters)
+        stream, sp = stream_arg(stream, lappr_fi.device)
         ws = self._workspace(stream, self.workspace_bytes(ld, max_iterations))
-        check(_lib.load().qr_decode_batch_device(
-            self._h, int(B), int(ld), C.c_void_p(lappr_fi.data_ptr()), C.c_void_p(synd_fi.data_ptr()),
-            int(max_iterations), C.c_void_p(final_fi.data_ptr()), C.c_void_p(success.data_ptr()),
-            C.c_void_p(iters.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-            C.c_void_p(stream.cuda_stream)), "decode_device")
+        check(_lib.load().qr_decode_batch_device(self._h, int(B), int(ld), dptr(lappr_fi), dptr(synd_fi),
+                                                 int(max_iterations), dptr(final_fi), dptr(success), dptr(iters),
+                                                 dptr(ws), ws.numel(), sp), "decode_device")
         return final_fi, success, iters
+
+    def _outputs(self, what, B, lappr, final, final_name, final_shape, success, iters):
+        """The outputs of a device decode, allocated beside `lappr` where not given, and checked:
+        (final float64 of final_shape, success uint8 [>= B], iters int32 [>= B])."""
+        import torch
+
+        if final is None:
+            final = torch.empty_like(lappr)
+        if success is None:
+            success = torch.empty(B, dtype=torch.uint8, device=lappr.device)
+        if iters is None:
+            iters = torch.empty(B, dtype=torch.int32, device=lappr.device)
+        check_tensor(final, final_name, final_shape, torch.float64, self._device)
+        if success.numel() < B or iters.numel() < B:
+            raise ValueError(f"{what}: success/iters must hold at least B={B} entries")
+        check_tensor(success, "success", (success.numel(),), torch.uint8, self._device)
+        check_tensor(iters, "iters", (iters.numel(),), torch.int32, self._device)
+        return final, success, iters
 
     def frames_workspace_bytes(self, B: int, max_iterations: int) -> int:
         n = C.c_size_t()
@@ -262,35 +243,23 @@ class Decoder:
         current stream), workspace per stream as ``decode_device``."""
         import torch
 
-        from ._lib import check_tensor
-
-        dev = self._device
         if not isinstance(lappr, torch.Tensor) or lappr.dim() != 2 or lappr.shape[0] < 1:
             raise ValueError("decode_frames_device: lappr must be a 2-D tensor [B, V] with B >= 1")
         B = int(lappr.shape[0])
-        check_tensor(lappr, "lappr", (B, self._V), torch.float64, dev)
-        check_tensor(synd, "synd", (B, self._C), torch.uint8, dev)
-        tdev = lappr.device
-        if final is None:
-            final = torch.empty_like(lappr)
-        if success is None:
-            success = torch.empty(B, dtype=torch.uint8, device=tdev)
-        if iters is None:
-            iters = torch.empty(B, dtype=torch.int32, device=tdev)
-        if not isinstance(final, torch.Tensor) or final.dim() != 2 or final.shape[0] < B:
-            raise ValueError(f"decode_frames_device: final must hold at least B={B} rows of V")
-        check_tensor(final, "final", (final.shape[0], self._V), torch.float64, dev)
-        if success.numel() < B or iters.numel() < B:
-            raise ValueError(f"decode_frames_device: success/iters must hold at least B={B} entries")
-        check_tensor(success, "success", (success.numel(),), torch.uint8, dev)
-        check_tensor(iters, "iters", (iters.numel(),), torch.int32, dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(tdev)
+        check_tensor(lappr, "lappr", (B, self._V), torch.float64, self._device)
+        check_tensor(synd, "synd", (B, self._C), torch.uint8, self._device)
+        rows = B
+        if final is not None:   # any number of rows from B up
+            if not isinstance(final, torch.Tensor) or final.dim() != 2 or final.shape[0] < B:
+                raise ValueError(f"decode_frames_device: final must hold at least B={B} rows of V")
+            rows = final.shape[0]
+        final, success, iters = self._outputs("decode_frames_device", B, lappr, final, "final", (rows, self._V),
+                                              success, iters)
+        stream, sp = stream_arg(stream, lappr.device)
         ws = self._workspace(stream, self.frames_workspace_bytes(B, max_iterations))
-        check(_lib.load().qr_decode_frames_device(
-            self._h, B, C.c_void_p(lappr.data_ptr()), C.c_void_p(synd.data_ptr()), int(max_iterations),
-            C.c_void_p(final.data_ptr()), C.c_void_p(success.data_ptr()), C.c_void_p(iters.data_ptr()),
-            C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream.cuda_stream)), "decode_frames_device")
+        check(_lib.load().qr_decode_frames_device(self._h, B, dptr(lappr), dptr(synd), int(max_iterations), dptr(final),
+                                                  dptr(success), dptr(iters), dptr(ws), ws.numel(), sp),
+              "decode_frames_device")
         return final, success, iters
 
     def repack_stats(self, ld: int, max_iterations: int, stream=None):
@@ -299,14 +268,12 @@ class Decoder:
         for the device (a synchronous copy); call after the decode has completed."""
         import torch
 
-        if stream is None:
-            stream = torch.cuda.current_stream(torch.device("cuda", self._device))
-        ws = self._ws.get(int(stream.cuda_stream))
+        ws = self._ws.get(_stream_key(stream_arg(stream, torch.device("cuda", self._device))[0]))
         if ws is None:
             raise ValueError("repack_stats: no decode_device has run on this stream")
         out = (C.c_int32 * 4)()
-        check(_lib.load().qr_decode_repack_stats(self._h, int(ld), int(max_iterations), C.c_void_p(ws.data_ptr()),
-                                                 ws.numel(), out), "repack_stats")
+        check(_lib.load().qr_decode_repack_stats(self._h, int(ld), int(max_iterations), dptr(ws), ws.numel(), out),
+              "repack_stats")
         return (int(out[0]), int(out[1])), (int(out[2]), int(out[3]))
 
     #: how many per-stream workspaces a Decoder keeps (each is E*ld*8 bytes of messages)
@@ -323,7 +290,7 @@ class Decoder:
         only after the work already queued on its stream."""
         import torch
 
-        key = int(stream.cuda_stream)
+        key = _stream_key(stream)
         ws = self._ws.pop(key, None)
         if ws is None or ws.numel() < need:
             ws = None  # free the smaller one before allocating

@@ -27,7 +27,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import check, check_tensor, ptr
+from ._lib import bool_as_u8, check, check_2d, check_tensor, dptr, ptr, stream_arg
 
 __all__ = ["P_xhat", "mutual_information_X_Xhat", "montecarlo_information", "montecarlo_information_device",
            "which_mask", "mutual_information_base_scheme_arg", "mutual_information_base_scheme_arg_array",
@@ -82,12 +82,17 @@ def which_mask(which) -> int:
     return (1 if w[0] else 0) | (2 if w[1] else 0) | (4 if w[2] else 0)
 
 
+def _check_pX(p_Xhat, M, what="p_Xhat"):
+    pX = np.ascontiguousarray(np.asarray(p_Xhat, np.float64).ravel())
+    if pX.size != M:
+        raise ValueError(f"{what} has {pX.size} entries, the alphabet {M}")
+    return pX
+
+
 def _prepare(nm, p_Xhat):
     """Make the demapper handle ready for the estimator: the interpolation grid in HBM and the
     (p_Xhat, fwrd_transition_probability) tables; uploads only when p_Xhat changed."""
-    pX = np.ascontiguousarray(np.asarray(p_Xhat, np.float64).ravel())
-    if pX.size != nm.order:
-        raise ValueError(f"p_Xhat has {pX.size} entries, the alphabet {nm.order}")
+    pX = _check_pX(p_Xhat, nm.order)
     nm._device_grid()
     key = pX.tobytes()
     if getattr(nm, "_mi_key", None) != key:
@@ -124,9 +129,7 @@ def montecarlo_information_device(nm, p_Xhat, x_fi, y_fi, B, which=np.ones(3, dt
     to write them into, `out` a float64 (3, ld) tensor for the totals (columns [0, B) are written)."""
     import torch
 
-    if not isinstance(y_fi, torch.Tensor) or y_fi.dim() != 2:
-        raise ValueError("montecarlo_information_device: y_fi must be a 2-D tensor [S, ld]")
-    S, ld = y_fi.shape
+    S, ld = check_2d(y_fi, "montecarlo_information_device", "y_fi", "[S, ld]")
     if ld % 64 or not 0 < int(B) <= ld or S < 1:
         raise ValueError(f"montecarlo_information_device: need ld % 64 == 0, 0 < B <= ld, S >= 1 (B={B}, ld={ld}, S={S})")
     dev = nm._device
@@ -138,21 +141,19 @@ def montecarlo_information_device(nm, p_Xhat, x_fi, y_fi, B, which=np.ones(3, dt
     info = torch.empty((3, ld), dtype=torch.float64, device=y_fi.device) if out is None else out
     check_tensor(info, "out", (3, ld), torch.float64, dev)
     current = torch.cuda.current_stream(y_fi.device)
-    if stream is None:
-        stream = current
+    stream, sp = stream_arg(stream, y_fi.device)
     want_terms = terms is not False and terms is not None
     if want_terms:
         t = torch.empty((3, S, ld), dtype=torch.float64, device=y_fi.device) if terms is True else terms
         check_tensor(t, "terms", (3, S, ld), torch.float64, dev)
-        d_terms, d_ws, ws_bytes = C.c_void_p(t.data_ptr()), None, 0
+        d_terms, d_ws, ws_bytes = dptr(t), None, 0
     else:
         need = C.c_size_t(0)
         check(L.qr_mi_workspace_size(int(ld), int(S), C.byref(need)), "mi_workspace_size")
         t = torch.empty((need.value,), dtype=torch.uint8, device=y_fi.device)
-        d_terms, d_ws, ws_bytes = None, C.c_void_p(t.data_ptr()), need.value
-    check(L.qr_mi_montecarlo_device(nm.handle, mask, int(B), int(ld), int(S), C.c_void_p(x_fi.data_ptr()),
-                                    C.c_void_p(y_fi.data_ptr()), C.c_void_p(info.data_ptr()), d_terms, d_ws, ws_bytes,
-                                    C.c_void_p(stream.cuda_stream)), "montecarlo_information_device")
+        d_terms, d_ws, ws_bytes = None, dptr(t), need.value
+    check(L.qr_mi_montecarlo_device(nm.handle, mask, int(B), int(ld), int(S), dptr(x_fi), dptr(y_fi), dptr(info), d_terms,
+                                    d_ws, ws_bytes, sp), "montecarlo_information_device")
     if stream != current:   # the buffer came from the current stream's pool: keep it until `stream` is done with it
         t.record_stream(stream)
     return (info[:, :B], t) if want_terms else info[:, :B]
@@ -171,13 +172,6 @@ def _check_limit(limit) -> int:
     if int(limit) < 1:
         raise ValueError(f"limit must be at least 1, got {limit}")
     return int(limit)
-
-
-def _check_pX(p_Xhat, M, what="p_Xhat"):
-    pX = np.ascontiguousarray(np.asarray(p_Xhat, np.float64).ravel())
-    if pX.size != M:
-        raise ValueError(f"{what} has {pX.size} entries, the alphabet {M}")
-    return pX
 
 
 QUAD_MESSAGES = {
@@ -266,10 +260,8 @@ def mutual_information_quad_batch(kind, nms, p_Xhats=None, sign_configs=None, *,
         pX = np.ascontiguousarray(np.stack([_check_pX(r, M, f"p_Xhats[{q}]") for q, r in enumerate(rows)]))
     cfg = None
     if sign_configs is not None:
-        cfg = np.asarray(sign_configs)
-        if cfg.dtype == np.bool_:
-            cfg = cfg.view(np.uint8)
-        if cfg.dtype != np.uint8 or cfg.shape != (P, M):
+        cfg = bool_as_u8(sign_configs)
+        if cfg.dtype != np.uint8 or cfg.shape != (P, M):   # rank 2: not as_buffer's 1-D or ravelled rule
             raise ValueError(f"sign_configs must be uint8 of shape ({P}, {M}), got {cfg.dtype} {cfg.shape}")
         cfg = np.ascontiguousarray(cfg)
     for nm in nms:
@@ -277,7 +269,7 @@ def mutual_information_quad_batch(kind, nms, p_Xhats=None, sign_configs=None, *,
     handles = (C.c_void_p * P)(*[nm.handle for nm in nms])
     check(_lib.load().qr_mi_quad_batch(handles, None if pX is None else ptr(pX), None if cfg is None else ptr(cfg), P, k,
                                        float(epsabs), float(epsrel), limit, ptr(I), ptr(abserr), ptr(neval), ptr(ier),
-                                       None if stream is None else C.c_void_p(stream.cuda_stream)),
+                                       None if stream is None else stream_arg(stream, None)[1]),
           "mutual_information_quad_batch")
     return I, abserr, neval, ier
 

@@ -26,13 +26,29 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import check, check_tensor, ptr
+from ._lib import as_buffer, check, check_2d, check_batch, check_tensor, dptr, ptr, stream_arg
 from .alphabet import PAMAlphabet
 
 
-def _check_batch(B, ld, what):
-    if ld % 64 or not 0 < int(B) <= ld:
-        raise ValueError(f"{what}: need ld % 64 == 0 and 0 < B <= ld (B={B}, ld={ld})")
+def _pair(n, j, size_message):
+    """The (double, long) array pair of the reference's array methods, ravelled; equal sizes."""
+    n = as_buffer(n, np.float64, flat=True)
+    j = as_buffer(j, np.int64, flat=True)
+    if n.size != j.size:
+        raise ValueError(size_message)
+    return n, j
+
+
+def _frame_row(values, dtype, device):
+    """One frame of S values laid along the frame axis as ONE row of S "frames" ([1, ld] in HBM, ld = S
+    rounded up to 64, zero padded): the per-symbol maps are elementwise, so this is S lanes of work
+    instead of 64 columns per symbol."""
+    import torch
+
+    v = torch.from_numpy(np.ascontiguousarray(np.asarray(values).ravel().astype(dtype, copy=False)))
+    row = torch.zeros((1, max(64, -(-v.numel() // 64) * 64)), dtype=v.dtype, device=device)
+    row[0, :v.numel()] = v.to(device)
+    return row
 
 
 def F_Z(z, mu, sigma):
@@ -40,20 +56,14 @@ def F_Z(z, mu, sigma):
     z, with scipy's erf as the reference.  Off the hot path (a host helper)."""
     from scipy.special import erf
 
-    z = np.asarray(z)
-    if z.dtype != np.float64:
-        raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{z.dtype}'")
-    z = np.ascontiguousarray(z.ravel())
+    z = as_buffer(z, np.float64, flat=True)
     return 0.5 * (1 + erf((z - float(mu)) / (math.sqrt(2) * float(sigma))))
 
 
 def view_dist_cut(x):
     """noisemapper.pyx:82-98 (``__view_dist_cut``): every x clipped to the probability range,
     0 below 0, 1 from 1 on (NaN stays NaN, as the reference's comparisons leave it)."""
-    x = np.asarray(x)
-    if x.dtype != np.float64:
-        raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{x.dtype}'")
-    x = np.ascontiguousarray(x.ravel())
+    x = as_buffer(x, np.float64, flat=True)
     return np.where(x < 0, 0.0, np.where(x >= 1, 1.0, x))
 
 
@@ -109,14 +119,9 @@ class NoiseMapper:
         if sign_config is None:  # :115-120
             sc = np.zeros(pa.order, dtype=np.uint8)
         else:
-            sc = np.asarray(sign_config)
-            if sc.dtype == np.bool_:
-                sc = sc.view(np.uint8)
-            if sc.dtype != np.uint8:
-                raise ValueError(f"Buffer dtype mismatch, expected 'unsigned char' but got '{sc.dtype}'")
+            sc = as_buffer(sign_config, np.uint8, flat=True)
             if sc.size < pa.order:
                 raise ValueError("Not enough data for a monotonicity sign configuration")
-            sc = np.ascontiguousarray(sc)
         self.sign_config = sc
         self.order = pa.order
         self.half_order = pa.order >> 1
@@ -200,10 +205,7 @@ class NoiseMapper:
     # ------------------------------------- CDF and its inverse (GPU, scalar API)
     def F_Y(self, y):
         """noisemapper.pyx:264-275: the uniformly weighted mixture CDF at every y."""
-        y = np.asarray(y)
-        if y.dtype != np.float64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{y.dtype}'")
-        y = np.ascontiguousarray(y.ravel())
+        y = as_buffer(y, np.float64, flat=True)
         out = np.empty(y.size, np.float64)
         if y.size:
             check(_lib.load().qr_F_Y_host(self._h, y.size, ptr(y), ptr(out)), "F_Y")
@@ -221,16 +223,7 @@ class NoiseMapper:
 
     def demap_noise_search(self, n_hat, symb, y_accuracy=1e-9):
         """noisemapper.pyx:407-419: g_inv_search over arrays."""
-        n_hat = np.asarray(n_hat)
-        symb = np.asarray(symb)
-        if n_hat.dtype != np.float64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{n_hat.dtype}'")
-        if symb.dtype != np.int64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'long' but got '{symb.dtype}'")
-        if n_hat.size != symb.size:
-            raise ValueError("Sizes do not match")
-        n_hat = np.ascontiguousarray(n_hat.ravel())
-        symb = np.ascontiguousarray(symb.ravel())
+        n_hat, symb = _pair(n_hat, symb, "Sizes do not match")
         out = np.empty(n_hat.size, np.float64)
         if n_hat.size:
             check(_lib.load().qr_g_inv_search_host(self._h, n_hat.size, ptr(n_hat), ptr(symb), float(y_accuracy),
@@ -240,16 +233,7 @@ class NoiseMapper:
     # ------------------------------------------------------- hot path (GPU)
     def demap_lappr_array(self, n, j):
         """noisemapper.pyx:544-559: LAPPRs [S*bps], out[s*bps + k] = Gray bit k of symbol s."""
-        n = np.asarray(n)
-        j = np.asarray(j)
-        if n.dtype != np.float64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{n.dtype}'")
-        if j.dtype != np.int64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'long' but got '{j.dtype}'")
-        if n.size != j.size:
-            raise ValueError("Sizes of transformed noise vector and tx symbols do not match")
-        n = np.ascontiguousarray(n.ravel())
-        j = np.ascontiguousarray(j.ravel())
+        n, j = _pair(n, j, "Sizes of transformed noise vector and tx symbols do not match")
         out = np.empty(n.size * self.bit_per_symbol, np.float64)
         if n.size:
             check(_lib.load().qr_demap_host(self._h, n.size, ptr(n), ptr(j), ptr(out)), "demap_lappr_array")
@@ -286,16 +270,7 @@ class NoiseMapper:
 
     def demap_noise(self, n_hat, symb):
         """noisemapper.pyx:391-403: g_inv over arrays."""
-        n_hat = np.asarray(n_hat)
-        symb = np.asarray(symb)
-        if n_hat.dtype != np.float64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{n_hat.dtype}'")
-        if symb.dtype != np.int64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'long' but got '{symb.dtype}'")
-        if n_hat.size != symb.size:
-            raise ValueError("Sizes do not match")
-        n_hat = np.ascontiguousarray(n_hat.ravel())
-        symb = np.ascontiguousarray(symb.ravel())
+        n_hat, symb = _pair(n_hat, symb, "Sizes do not match")
         out = np.empty(n_hat.size, np.float64)
         if n_hat.size:
             self._device_grid()
@@ -305,16 +280,7 @@ class NoiseMapper:
     def demap_lappr_simplified_array(self, n, j):
         """noisemapper.pyx:605-620 ("Formulation 1"): LAPPRs [S*bps], out[s*bps + k] = Gray bit k
         of symbol s, from the interpolated g_inv."""
-        n = np.asarray(n)
-        j = np.asarray(j)
-        if n.dtype != np.float64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{n.dtype}'")
-        if j.dtype != np.int64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'long' but got '{j.dtype}'")
-        if n.size != j.size:
-            raise ValueError("Sizes of transformed noise vector and tx symbols do not match")
-        n = np.ascontiguousarray(n.ravel())
-        j = np.ascontiguousarray(j.ravel())
+        n, j = _pair(n, j, "Sizes of transformed noise vector and tx symbols do not match")
         out = np.empty(n.size * self.bit_per_symbol, np.float64)
         if n.size:
             self._device_grid()
@@ -327,19 +293,13 @@ class NoiseMapper:
         return self.demap_lappr_simplified_array(np.array([float(n)]), np.array([int(j)], np.int64))
 
     # ----------------------------------------------- Bob side (GPU, batched)
-    # Single-frame (reference-style) calls: the per-symbol maps are elementwise, so one
-    # frame of S symbols is laid out along the frame axis as ONE symbol row of S "frames"
-    # (ld = S rounded up to 64): S lanes of work instead of 64 columns per symbol.
+    # Single-frame (reference-style) calls run one _frame_row through the batched kernels.
     def _bob_host(self, y):
         import torch
 
-        y = np.ascontiguousarray(np.asarray(y, np.float64).ravel())
-        S = y.size
-        ld = max(64, -(-S // 64) * 64)
+        S = np.size(y)
         dev = torch.device("cuda", self._device)
-        yt = torch.zeros((1, ld), dtype=torch.float64, device=dev)
-        yt[0, :S] = torch.from_numpy(y).to(dev)
-        xh, nh, w = self.bob_map_device(yt, S)
+        xh, nh, w = self.bob_map_device(_frame_row(y, np.float64, dev), S)
         torch.cuda.synchronize(dev)
         # word rows k = Gray bit k of the row's symbol; symbol s's bits are s * bps + k
         return (xh[0, :S].cpu().numpy(), nh[0, :S].cpu().numpy(),
@@ -353,103 +313,74 @@ class NoiseMapper:
         """noisemapper.pyx:373-388: n[j] = g(y[j], index[j])."""
         import torch
 
-        idx = np.asarray(index)
-        y = np.asarray(y_samples, np.float64)
-        if y.size != idx.size:
+        S = np.size(y_samples)
+        if S != np.size(index):
             raise ValueError("Input vectors sizes do not match")
-        S = y.size
-        ld = max(64, -(-S // 64) * 64)  # one frame along the frame axis (see _bob_host)
         dev = torch.device("cuda", self._device)
-        yt = torch.zeros((1, ld), dtype=torch.float64, device=dev)
-        yt[0, :S] = torch.from_numpy(np.ascontiguousarray(y.ravel())).to(dev)
-        it = torch.zeros((1, ld), dtype=torch.int64, device=dev)
-        it[0, :S] = torch.from_numpy(np.ascontiguousarray(idx.ravel().astype(np.int64))).to(dev)
-        nh = self.map_noise_device(yt, it, S)
+        nh = self.map_noise_device(_frame_row(y_samples, np.float64, dev), _frame_row(index, np.int64, dev), S)
         torch.cuda.synchronize(dev)
         return nh[0, :S].cpu().numpy()
+
+    def _check_rows(self, what, B, name, t, index_name=None, index=None):
+        """The checks of every batched method on its float64 [S, ld] input (and the int64 one beside
+        it, if any) -> (S, ld)."""
+        import torch
+
+        S, ld = check_2d(t, what, name, "[S, ld]")
+        check_batch(B, ld, what)
+        check_tensor(t, name, (S, ld), torch.float64, self._device)
+        if index_name is not None:
+            check_tensor(index, index_name, (S, ld), torch.int64, self._device)
+        return S, ld
 
     def map_noise_device(self, y_fi, index_fi, B: int, stream=None):
         """y_fi float64 [S, ld], index_fi int64 [S, ld] -> n_hat float64 [S, ld]."""
         import torch
 
-        if not isinstance(y_fi, torch.Tensor) or y_fi.dim() != 2:
-            raise ValueError("map_noise_device: y_fi must be a 2-D tensor [S, ld]")
-        S, ld = y_fi.shape
-        _check_batch(B, ld, "map_noise_device")
-        check_tensor(y_fi, "y_fi", (S, ld), torch.float64, self._device)
-        check_tensor(index_fi, "index_fi", (S, ld), torch.int64, self._device)
+        S, ld = self._check_rows("map_noise_device", B, "y_fi", y_fi, "index_fi", index_fi)
         nh = torch.empty((S, ld), dtype=torch.float64, device=y_fi.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(y_fi.device)
-        check(_lib.load().qr_map_noise_device(self._h, int(B), int(ld), int(S), C.c_void_p(y_fi.data_ptr()),
-                                              C.c_void_p(index_fi.data_ptr()), C.c_void_p(nh.data_ptr()),
-                                              C.c_void_p(stream.cuda_stream)), "map_noise_device")
+        check(_lib.load().qr_map_noise_device(self._h, int(B), int(ld), int(S), dptr(y_fi), dptr(index_fi), dptr(nh),
+                                              stream_arg(stream, y_fi.device)[1]), "map_noise_device")
         return nh
 
     # ------------------------------------------------- device (HBM) batches
-    def demap_device(self, n_fi, j_fi, B: int, alpha: float = 1.0, out=None, stream=None):
-        """n_fi float64 [S, ld], j_fi int64 [S, ld] -> LAPPRs float64 [S*bps, ld]
-        (the decoder's frame-innermost input), scaled by alpha."""
+    def _demap_device(self, simplified, n_fi, j_fi, B, alpha, out, stream):
         import torch
 
-        if not isinstance(n_fi, torch.Tensor) or n_fi.dim() != 2:
-            raise ValueError("demap_device: n_fi must be a 2-D tensor [S, ld]")
-        S, ld = n_fi.shape
-        _check_batch(B, ld, "demap_device")
-        check_tensor(n_fi, "n_fi", (S, ld), torch.float64, self._device)
-        check_tensor(j_fi, "j_fi", (S, ld), torch.int64, self._device)
+        what = "demap_simplified_device" if simplified else "demap_device"
+        S, ld = self._check_rows(what, B, "n_fi", n_fi, "j_fi", j_fi)
         if out is None:
             out = torch.empty((S * self.bit_per_symbol, ld), dtype=torch.float64, device=n_fi.device)
         check_tensor(out, "out", (S * self.bit_per_symbol, ld), torch.float64, self._device)
-        if stream is None:
-            stream = torch.cuda.current_stream(n_fi.device)
-        check(_lib.load().qr_demap_batch_device(self._h, int(B), int(ld), int(S), C.c_void_p(n_fi.data_ptr()),
-                                                C.c_void_p(j_fi.data_ptr()), float(alpha),
-                                                C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)),
-              "demap_device")
+        L = _lib.load()
+        if simplified:
+            self._device_grid()
+        entry = L.qr_demap_simplified_batch_device if simplified else L.qr_demap_batch_device
+        check(entry(self._h, int(B), int(ld), int(S), dptr(n_fi), dptr(j_fi), float(alpha), dptr(out),
+                    stream_arg(stream, n_fi.device)[1]), what)
         return out
+
+    def demap_device(self, n_fi, j_fi, B: int, alpha: float = 1.0, out=None, stream=None):
+        """n_fi float64 [S, ld], j_fi int64 [S, ld] -> LAPPRs float64 [S*bps, ld]
+        (the decoder's frame-innermost input), scaled by alpha."""
+        return self._demap_device(False, n_fi, j_fi, B, alpha, out, stream)
 
     def demap_simplified_device(self, n_fi, j_fi, B: int, alpha: float = 1.0, out=None, stream=None):
         """demap_device with the formulation-1 demapper (noisemapper.pyx:563-620): n_fi float64
         [S, ld], j_fi int64 [S, ld] -> LAPPRs float64 [S*bps, ld], scaled by alpha."""
-        import torch
-
-        if not isinstance(n_fi, torch.Tensor) or n_fi.dim() != 2:
-            raise ValueError("demap_simplified_device: n_fi must be a 2-D tensor [S, ld]")
-        S, ld = n_fi.shape
-        _check_batch(B, ld, "demap_simplified_device")
-        check_tensor(n_fi, "n_fi", (S, ld), torch.float64, self._device)
-        check_tensor(j_fi, "j_fi", (S, ld), torch.int64, self._device)
-        if out is None:
-            out = torch.empty((S * self.bit_per_symbol, ld), dtype=torch.float64, device=n_fi.device)
-        check_tensor(out, "out", (S * self.bit_per_symbol, ld), torch.float64, self._device)
-        if stream is None:
-            stream = torch.cuda.current_stream(n_fi.device)
-        self._device_grid()
-        check(_lib.load().qr_demap_simplified_batch_device(
-            self._h, int(B), int(ld), int(S), C.c_void_p(n_fi.data_ptr()), C.c_void_p(j_fi.data_ptr()),
-            float(alpha), C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)), "demap_simplified_device")
-        return out
+        return self._demap_device(True, n_fi, j_fi, B, alpha, out, stream)
 
     def bob_map_device(self, y_fi, B: int, stream=None):
         """y_fi float64 [S, ld] -> (x_hat int64 [S, ld], n_hat float64 [S, ld], word uint8 [S*bps, ld])."""
         import torch
 
-        if not isinstance(y_fi, torch.Tensor) or y_fi.dim() != 2:
-            raise ValueError("bob_map_device: y_fi must be a 2-D tensor [S, ld]")
-        S, ld = y_fi.shape
-        _check_batch(B, ld, "bob_map_device")
-        check_tensor(y_fi, "y_fi", (S, ld), torch.float64, self._device)
+        S, ld = self._check_rows("bob_map_device", B, "y_fi", y_fi)
         dev = y_fi.device
         xh = torch.empty((S, ld), dtype=torch.int64, device=dev)
         nh = torch.empty((S, ld), dtype=torch.float64, device=dev)
         w = torch.zeros((S * self.bit_per_symbol, ld), dtype=torch.uint8, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        check(_lib.load().qr_bob_map_device(self._h, int(B), int(ld), int(S), C.c_void_p(y_fi.data_ptr()),
-                                            C.c_void_p(xh.data_ptr()), C.c_void_p(nh.data_ptr()),
-                                            C.c_void_p(w.data_ptr()), C.c_void_p(stream.cuda_stream)),
-              "bob_map_device")
+        check(_lib.load().qr_bob_map_device(self._h, int(B), int(ld), int(S), dptr(y_fi), dptr(xh), dptr(nh), dptr(w),
+                                            stream_arg(stream, dev)[1]), "bob_map_device")
         return xh, nh, w
 
 

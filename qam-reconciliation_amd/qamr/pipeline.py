@@ -19,12 +19,12 @@ and the oracle, not on random streams.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from ._lib import dptr, stream_arg
 from .alphabet import PAMAlphabet
 from .decoder import Decoder
 from .noisemapper import NoiseMapper
@@ -56,6 +56,38 @@ def check_demapper(demapper: str) -> str:
 
 def leading_dim(B: int) -> int:
     return ((B + 255) // 256) * 256 if B >= 256 else ((B + 63) // 64) * 64
+
+
+# ------------------------------------------------- stages shared with qamr.sim and qamr.sim_binary
+def draw_symbols(p, S: int, ld: int, gen, uniform: bool):
+    """Symbol indices int64 [S, ld] drawn from the probabilities `p` (a device tensor): one randint
+    when they are uniform, else one multinomial."""
+    import torch
+
+    if uniform:
+        return torch.randint(0, p.numel(), (S, ld), generator=gen, device=p.device, dtype=torch.int64)
+    return torch.multinomial(p, S * ld, replacement=True, generator=gen).view(S, ld)
+
+
+def syndrome_device(dec: Decoder, word_fi, B: int, ld: int, stream=None):
+    """word_fi uint8 [V, ld] -> synd uint8 [C, ld] = H word of the first B columns (k_syndrome)."""
+    import torch
+
+    synd = torch.empty((dec.cnum, ld), dtype=torch.uint8, device=word_fi.device)
+    _lib.check(_lib.load().qr_syndrome_device(dec.handle, B, ld, dptr(word_fi), dptr(synd),
+                                              stream_arg(stream, word_fi.device)[1]), "syndrome")
+    return synd
+
+
+def count_errors_device(neg: bool, B: int, ld: int, K: int, final, word, success, iters, ferr, counters, stream=None):
+    """Per-frame bit errors of the first K bits into ferr int32 [B] and {bit_errors, frame_errors,
+    successes, iter_sum, frames} added to counters int64 [5]; neg: the `final < 0` rule of the
+    binary-channel scripts in place of reconciliation.pyx:149-157."""
+    L = _lib.load()
+    entry = L.qr_count_errors_neg_device if neg else L.qr_count_errors_device
+    _lib.check(entry(B, ld, K, dptr(final), dptr(word), dptr(success), dptr(iters), dptr(ferr), dptr(counters),
+                     stream_arg(stream, final.device)[1]), "count_neg" if neg else "count")
+    return counters
 
 
 @dataclass
@@ -103,25 +135,15 @@ class SofteningPipeline:
     def generate(self, gen=None) -> Batch:
         import torch
 
-        S, ld, dev = self.S, self.ld, self.device
-        if self._uniform:
-            x = torch.randint(0, self.pa.order, (S, ld), generator=gen, device=dev, dtype=torch.int64)
-        else:
-            x = torch.multinomial(self._p, S * ld, replacement=True, generator=gen).view(S, ld)
-        y = self._a[x] + self.nm.noise_sigma * torch.randn((S, ld), generator=gen, device=dev, dtype=torch.float64)
+        S, ld = self.S, self.ld
+        x = draw_symbols(self._p, S, ld, gen, self._uniform)
+        y = self._a[x] + self.nm.noise_sigma * torch.randn((S, ld), generator=gen, device=self.device,
+                                                           dtype=torch.float64)
         _, nhat, word = self.nm.bob_map_device(y, self.B)
-        synd = self.dec_syndrome(word)
-        return Batch(self.B, ld, x, nhat, word, synd)
+        return Batch(self.B, ld, x, nhat, word, self.dec_syndrome(word))
 
     def dec_syndrome(self, word_fi):
-        import torch
-
-        out = torch.empty((self.C, self.ld), dtype=torch.uint8, device=self.device)
-        st = torch.cuda.current_stream(self.device)
-        _lib.check(_lib.load().qr_syndrome_device(self.dec.handle, self.B, self.ld, C.c_void_p(word_fi.data_ptr()),
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream)),
-                   "syndrome")
-        return out
+        return syndrome_device(self.dec, word_fi, self.B, self.ld)
 
     # ---------------------------------------------------------- hot path
     def demap(self, batch: Batch, out=None):
@@ -134,14 +156,8 @@ class SofteningPipeline:
 
     def count(self, final_fi, batch: Batch, success, iters):
         """Accumulate {bit_errors, frame_errors, successes, iter_sum, frames}."""
-        import torch
-
-        st = torch.cuda.current_stream(self.device)
-        _lib.check(_lib.load().qr_count_errors_device(
-            batch.B, batch.ld, self.K, C.c_void_p(final_fi.data_ptr()), C.c_void_p(batch.word.data_ptr()),
-            C.c_void_p(success.data_ptr()), C.c_void_p(iters.data_ptr()), C.c_void_p(self._ferr.data_ptr()),
-            C.c_void_p(self.counters.data_ptr()), C.c_void_p(st.cuda_stream)), "count")
-        return self.counters
+        return count_errors_device(False, batch.B, batch.ld, self.K, final_fi, batch.word, success, iters, self._ferr,
+                                   self.counters)
 
     def run_batch(self, gen=None):
         b = self.generate(gen)

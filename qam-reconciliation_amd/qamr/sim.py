@@ -20,17 +20,18 @@ RNG streams are torch's (per seed, rank and batch), not numpy's.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib, dist
+from ._lib import dptr, stream_arg
 from .alphabet import PAMAlphabet
 from .decoder import Decoder
 from .noisemapper import NoiseMapper
-from .pipeline import alternating_config, check_demapper, leading_dim
+from .pipeline import (alternating_config, check_demapper, count_errors_device, draw_symbols, leading_dim,
+                       syndrome_device)
 
 MODES = ("softening", "direct", "hard")
 
@@ -64,33 +65,21 @@ class Simulator:
 
     # ---------------------------------------------------------------- pieces
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream_arg(None, self.device)[1]
 
     def _symbols(self, S, ld, gen):
-        import torch
-
-        if self._uniform:
-            return torch.randint(0, self.pa.order, (S, ld), generator=gen, device=self.device, dtype=torch.int64)
-        return torch.multinomial(self._p, S * ld, replacement=True, generator=gen).view(S, ld)
+        return draw_symbols(self._p, S, ld, gen, self._uniform)
 
     def _bits(self, x, B, ld):
         import torch
 
         w = torch.empty((self.S * self.pa.bit_per_symbol, ld), dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.load().qr_symbols_to_bits_device(self.pa.bit_per_symbol, B, ld, self.S,
-                                                         C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()),
+        _lib.check(_lib.load().qr_symbols_to_bits_device(self.pa.bit_per_symbol, B, ld, self.S, dptr(x), dptr(w),
                                                          self._stream()), "symbols_to_bits")
         return w
 
     def _synd(self, word, B, ld):
-        import torch
-
-        s = torch.empty((self.C, ld), dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.load().qr_syndrome_device(self.dec.handle, B, ld, C.c_void_p(word.data_ptr()),
-                                                  C.c_void_p(s.data_ptr()), self._stream()), "syndrome")
-        return s
+        return syndrome_device(self.dec, word, B, ld)
 
     def frames(self, nm: NoiseMapper, B: int, gen, two_variance: float):
         """One batch of inputs for the selected mode: (lappr [V, ld], synd [C, ld], word [V, ld], ld)."""
@@ -112,15 +101,13 @@ class Simulator:
         elif self.mode == "direct":                        # reconciliation.pyx:209-221
             word = self._bits(x, B, ld)
             synd = self._synd(word, B, ld)
-            _lib.check(_lib.load().qr_direct_lappr_device(nm.handle, float(two_variance), B, ld, S,
-                                                          C.c_void_p(y.data_ptr()), C.c_void_p(lappr.data_ptr()),
+            _lib.check(_lib.load().qr_direct_lappr_device(nm.handle, float(two_variance), B, ld, S, dptr(y), dptr(lappr),
                                                           self._stream()), "direct_lappr")
         else:                                              # reconciliation.pyx:290-303
             xh, _, word = nm.bob_map_device(y, B)
             synd = self._synd(word, B, ld)
             table = torch.tensor(np.ascontiguousarray(nm.bare_llr_table), dtype=torch.float64, device=self.device)
-            _lib.check(_lib.load().qr_bare_llr_device(self.pa.bit_per_symbol, C.c_void_p(table.data_ptr()), B, ld,
-                                                      S, C.c_void_p(x.data_ptr()), C.c_void_p(lappr.data_ptr()),
+            _lib.check(_lib.load().qr_bare_llr_device(self.pa.bit_per_symbol, dptr(table), B, ld, S, dptr(x), dptr(lappr),
                                                       self._stream()), "bare_llr")
         return lappr, synd, word, ld
 
@@ -136,31 +123,21 @@ class Simulator:
         fin, succ, its = self.dec.decode_device(lappr, synd, B, self.max_iterations)
         ferr = torch.empty(B, dtype=torch.int32, device=self.device)
         delta = torch.zeros(5, dtype=torch.int64, device=self.device)
-        _lib.check(_lib.load().qr_count_errors_device(
-            B, ld, self.K, C.c_void_p(fin.data_ptr()), C.c_void_p(word.data_ptr()),
-            C.c_void_p(succ.data_ptr()), C.c_void_p(its.data_ptr()), C.c_void_p(ferr.data_ptr()),
-            C.c_void_p(delta.data_ptr()), self._stream()), "count")
+        count_errors_device(False, B, ld, self.K, fin, word, succ, its, ferr, delta)
         return ferr, succ[:B], its[:B], delta
 
     def run_snr(self, snr_dB: float, simulation_loops: int, ferr_count_min: int, seed: int = 0, hook=None):
         """Frames until `simulation_loops` or the early stop; returns
         (snr_dB, ber, fer, avg_iterations_of_successes).  hook(batch_index, lappr, synd, word, B):
         optional view of every shard's inputs (tests)."""
-        world, rank, _ = dist.env_world()
         Es = self.pa.variance
         two_var = Es * (10 ** (-snr_dB / 10))          # reconciliation.pyx:191-192, 272-273
         N0 = Es * (10 ** (-snr_dB / 10)) / 2           # reconciliation.pyx:109-110
         cfg = self.cfg if self.mode == "softening" else None
         nm = NoiseMapper(self.pa, N0, cfg, device=self._dev_index)
 
-        def frame_fn(bidx, start, B):
-            import torch
-
-            gen = torch.Generator(device=self.device).manual_seed(dist.rank_seed(seed, rank, bidx))
-            h = None if hook is None else (lambda l, s, w, b: hook(bidx, l, s, w, b))
-            return self.batch_results(nm, B, gen, two_var, h)
-
-        be, fe, su, it, fr = run_frames(frame_fn, self.batch, simulation_loops, ferr_count_min, self.device)
+        be, fe, su, it, fr = run_seeded(lambda B, gen, h: self.batch_results(nm, B, gen, two_var, h), seed, hook,
+                                        self.batch, simulation_loops, ferr_count_min, self.device)
         return (snr_dB, be / (fr * self.K), fe / fr, 0 if su == 0 else it / su)
 
 
@@ -261,6 +238,23 @@ def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int,
         done += n_global
         bidx += 1
     return [int(v) for v in total.cpu().numpy()]
+
+
+def run_seeded(batch_fn, seed: int, hook, batch: int, simulation_loops: int, ferr_count_min: int, device,
+               rule: StopRule | None = None):
+    """run_frames over batch_fn(B, gen, hook(inputs..., B) or None) -> (ferr, succ, its, delta): every batch gets
+    its own generator, seeded by (seed, rank, batch index), and `hook` is called with the batch index
+    first."""
+    _, rank, _ = dist.env_world()
+
+    def frame_fn(bidx, start, B):
+        import torch
+
+        gen = torch.Generator(device=device).manual_seed(dist.rank_seed(seed, rank, bidx))
+        h = None if hook is None else (lambda l, s, w, b: hook(bidx, l, s, w, b))
+        return batch_fn(B, gen, h)
+
+    return run_frames(frame_fn, batch, simulation_loops, ferr_count_min, device, rule)
 
 
 def simulate_softening_snr_dB(snr_dB, dec, bps, nmconfig, decoder_iterations, simulation_loops, ferr_count_min,

@@ -11,15 +11,15 @@ script's own stopping rule).  RNG streams are torch's (per seed, rank and batch)
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 
-from . import _lib, dist
+from . import _lib
+from ._lib import dptr, stream_arg
 from .decoder import Decoder
-from .pipeline import leading_dim
-from .sim import StopRule, run_frames
+from .pipeline import count_errors_device, leading_dim, syndrome_device
+from .sim import StopRule, run_seeded
 
 CHANNELS = ("biawgn", "biawgn_hard", "bsc")
 
@@ -81,9 +81,7 @@ class BinaryChannelSimulator:
         self.device = torch.device("cuda", device)
 
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream_arg(None, self.device)[1]
 
     def frames(self, point: float, B: int, gen):
         """One batch of inputs at `point` (dB, or the raw BER of the BSC):
@@ -93,21 +91,17 @@ class BinaryChannelSimulator:
         L = _lib.load()
         ld = leading_dim(B)
         word = torch.randint(0, 2, (self.V, ld), generator=gen, device=self.device, dtype=torch.uint8)
-        synd = torch.empty((self.C, ld), dtype=torch.uint8, device=self.device)
-        _lib.check(L.qr_syndrome_device(self.dec.handle, B, ld, C.c_void_p(word.data_ptr()),
-                                        C.c_void_p(synd.data_ptr()), self._stream()), "syndrome")
+        synd = syndrome_device(self.dec, word, B, ld)
         llr = torch.empty((self.V, ld), dtype=torch.float64, device=self.device)
         if self.channel == "bsc":
             u = torch.rand((self.V, ld), generator=gen, device=self.device, dtype=torch.float64)
-            _lib.check(L.qr_bsc_llr_device(bsc_coefficient(point), float(point), B, ld, self.V,
-                                           C.c_void_p(word.data_ptr()), C.c_void_p(u.data_ptr()),
-                                           C.c_void_p(llr.data_ptr()), None, self._stream()), "bsc_llr")
+            _lib.check(L.qr_bsc_llr_device(bsc_coefficient(point), float(point), B, ld, self.V, dptr(word), dptr(u),
+                                           dptr(llr), None, self._stream()), "bsc_llr")
         else:
             hard = self.channel == "biawgn_hard"
             coef, vsqrt = biawgn_coefficients(point, self.alpha, hard)
             z = torch.randn((self.V, ld), generator=gen, device=self.device, dtype=torch.float64)
-            _lib.check(L.qr_biawgn_llr_device(int(hard), coef, vsqrt, B, ld, self.V, C.c_void_p(word.data_ptr()),
-                                              C.c_void_p(z.data_ptr()), C.c_void_p(llr.data_ptr()),
+            _lib.check(L.qr_biawgn_llr_device(int(hard), coef, vsqrt, B, ld, self.V, dptr(word), dptr(z), dptr(llr),
                                               self._stream()), "biawgn_llr")
         return llr, synd, word, ld
 
@@ -122,10 +116,7 @@ class BinaryChannelSimulator:
         fin, succ, its = self.dec.decode_device(llr, synd, B, self.max_iterations)
         ferr = torch.empty(B, dtype=torch.int32, device=self.device)
         delta = torch.zeros(5, dtype=torch.int64, device=self.device)
-        _lib.check(_lib.load().qr_count_errors_neg_device(
-            B, ld, self.K, C.c_void_p(fin.data_ptr()), C.c_void_p(word.data_ptr()),
-            C.c_void_p(succ.data_ptr()), C.c_void_p(its.data_ptr()), C.c_void_p(ferr.data_ptr()),
-            C.c_void_p(delta.data_ptr()), self._stream()), "count_neg")
+        count_errors_device(True, B, ld, self.K, fin, word, succ, its, ferr, delta)
         return ferr, succ[:B], its[:B], delta
 
     def stop_rule(self, simulation_loops: int, min_errors: int) -> StopRule:
@@ -137,15 +128,7 @@ class BinaryChannelSimulator:
         """Frames until `simulation_loops` or the script's early stop; returns the script's tuple
         (point, ber, fer, avg_iterations_of_successes).  hook(batch_index, llr, synd, word, B):
         optional view of every shard's inputs (tests)."""
-        _, rank, _ = dist.env_world()
-
-        def frame_fn(bidx, start, B):
-            import torch
-
-            gen = torch.Generator(device=self.device).manual_seed(dist.rank_seed(seed, rank, bidx))
-            h = None if hook is None else (lambda l, s, w, b: hook(bidx, l, s, w, b))
-            return self.batch_results(point, B, gen, h)
-
-        be, fe, su, it, fr = run_frames(frame_fn, self.batch, simulation_loops, min_errors, self.device,
-                                        rule=self.stop_rule(simulation_loops, min_errors))
+        be, fe, su, it, fr = run_seeded(lambda B, gen, h: self.batch_results(point, B, gen, h), seed, hook, self.batch,
+                                        simulation_loops, min_errors, self.device,
+                                        self.stop_rule(simulation_loops, min_errors))
         return (point, be / (fr * self.K), fe / fr, 0 if su == 0 else it / su)
