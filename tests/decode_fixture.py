@@ -12,10 +12,17 @@ tests/test_decode_fixture_cpu.py.  Every case is computed once, shared and never
   repacks the device must decide, from the oracle's (success, iterations) alone.
 * the small codes of tests/test_gpu_repack_small_codes.py (``CODES``, ``small_code``,
   ``small_case``) and the regular (3, D) codes of tests/test_gpu_degree_matrix.py (``v_of``,
-  ``sigma_of``, ``case_of``); ``deal_sockets`` / ``scattered_code``: graph builders.
+  ``sigma_of``, ``case_of``), which tests/test_gpu_high_degrees.py extends to ``HIGH_DEGREES`` and
+  the high-degree mixed code (``himix_code``, ``himix_case``, ``assert_high_conditions``;
+  ``check_block``: the checks per workgroup of a sweep, for the ragged last workgroup);
+  ``deal_sockets`` / ``hub_code`` / ``scattered_code``: graph builders.
+* ``golden_cases`` / ``frame_digests`` / ``input_digest`` / ``GoldenDegrees`` /
+  ``assert_golden_records``: the cases whose decodes by the compiled reference are recorded in
+  tests/golden/decoder_degrees.npz, the one digest definition, and the fixture's reader.
 """
 import contextlib
 import functools
+import hashlib
 
 import numpy as np
 
@@ -155,17 +162,20 @@ def to_device(case, B, ld):
 
 def decode_and_compare(dec, L, S, B, mi, ref, tag, pad=PAD):
     """One decode into a final_fi filled with pad: all B frames equal the oracle's, the padding
-    columns [B, ld) keep the caller's value."""
+    columns [B, ld) keep the caller's value.  Returns the device's (success, iterations, final
+    LAPPRs [B, V]) on the host."""
     import torch
 
     s2, i2, f2 = ref
     fin = torch.full(tuple(L.shape), pad, dtype=torch.float64, device="cuda")
     _, succ, its = dec.decode_device(L, S, B, mi, final_fi=fin)
     torch.cuda.synchronize()
-    assert np.array_equal(succ.cpu().numpy(), s2[:B]), tag
-    assert np.array_equal(its.cpu().numpy(), i2[:B]), tag
-    assert_bit_exact(fin[:, :B].cpu().numpy().T, f2[:B])
+    got = succ.cpu().numpy(), its.cpu().numpy(), fin[:, :B].cpu().numpy().T
+    assert np.array_equal(got[0], s2[:B]), tag
+    assert np.array_equal(got[1], i2[:B]), tag
+    assert_bit_exact(got[2], f2[:B])
     assert bool((fin[:, B:] == pad).all()), tag
+    return got
 
 
 # ------------------------------------------------------------------ repack prediction
@@ -285,7 +295,13 @@ def v_of(D):
 
 def sigma_of(D):
     """Per-frame noise sigma ~ U(lo, hi), picked on the CPU from the oracle alone: both ranges
-    repack and end 64 columns wide, at least 5 distinct stop iterations."""
+    repack and end 64 columns wide, at least 5 distinct stop iterations.  D > 16 (the
+    runtime-degree kernel; lock-step, no repack): (0.25, 0.5), which meets assert_high_conditions;
+    seen at 30 iterations, special variant (D: successes of 512, distinct stop iterations >= 1):
+    17: 507, 10   18: 508, 9   22: 507, 17   27: 488, 18   30: 464, 17   33: 464, 16
+    65: 350, 15   100: 314, 16   255: 224, 8."""
+    if D > 16:
+        return (0.25, 0.5)
     return {2: (1.2, 2.0), 3: (0.9, 1.5), 4: (0.7, 1.1)}.get(D, (0.5, 0.8) if D <= 8 else (0.35, 0.6))
 
 
@@ -300,6 +316,203 @@ def case_of(D, variant):
     return case
 
 
+# ------------------------------------------------------------------ check degrees above 16
+# the runtime-degree kernel (decoder.hip k_check_generic): just past the templated range (17, 18),
+# the long DVB-S2 codes' degrees (18, 22, 27, 30), more than a wavefront (65), the largest (255)
+HIGH_DEGREES = (17, 18, 22, 27, 30, 33, 65, 100, 255)
+PLANTED = tuple(np.r_[0:4, H:H + 4, 8, 300].tolist())   # plant_special(h = H): codewords, special values
+
+# the high-degree mixed code: a packed class (7), a templated unpacked one (12) and three runtime
+# ones; a class of 65 checks (a wavefront plus one lane) and one of a single check; parallel
+# edges, every sixth variable isolated, variable 0 a hub of degree 70 (as few_fixture.mixed_code)
+HIMIX_V = 702
+HIMIX_CLASSES = [(7, 40), (12, 20), (17, 65), (30, 13), (64, 1)]
+HIMIX_HUB_DEGREE = 70
+HIMIX_SEED = 1730
+# per-frame noise sigma ~ U(lo, hi) of its frames, picked on the CPU from the oracle alone so that
+# assert_high_conditions holds; seen at 30 iterations (variant: successes of 512, distinct stop
+# iterations >= 1, frames running after iteration 29):
+#   (0.25, 0.5)  special: 508,  6,   4   clean: 510,  7,   2   (few late stops)
+#   (0.35, 0.6)  special: 481, 22,  32   clean: 482, 22,  31   <- chosen
+#   (0.4, 0.7)   special: 329, 23, 183   clean: 330, 23, 182
+HIMIX_SIGMA = (0.35, 0.6)
+
+
+def himix_code():
+    return hub_code(HIMIX_V, HIMIX_CLASSES, HIMIX_HUB_DEGREE, HIMIX_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def himix_case(variant):
+    """The 512 frames of (high-degree mixed code, variant).  plant_special's five values land on
+    the hub (variable 0), an isolated variable (2) and three ordinary ones."""
+    vid, cid = himix_code()
+    case = _variant_case(vid, cid, HIMIX_SIGMA, 1000 + HIMIX_SEED, variant)
+    assert case["orc"].vnum == HIMIX_V and case["orc"].cnum == sum(n for _, n in HIMIX_CLASSES)
+    return case
+
+
+def high_case(key, variant):
+    """case_of(D, variant) for a degree of HIGH_DEGREES, himix_case(variant) for "mix"."""
+    return himix_case(variant) if key == "mix" else case_of(key, variant)
+
+
+def high_classes(key):
+    """The check classes (degree, number of checks) of high_case(key, .)."""
+    return list(HIMIX_CLASSES) if key == "mix" else [(key, 3 * v_of(key) // key)]
+
+
+def check_block(ncols, n, check_ft=128, check_per=16, min_blocks=2048):
+    """(frame tile, checks per workgroup) of a check sweep over ncols frames of a class of n checks,
+    restated from decoder.hip make_geom: the tile is the largest of 256, 128, 64 that is at most
+    check_ft and divides ncols, a workgroup's 256 threads hold nsub = 256 / tile checks side by
+    side and per in a row; min_blocks > 0 lowers per, down to 1, while the launch has fewer
+    workgroups.  A class whose n is no multiple of per * nsub ends in a ragged workgroup."""
+    ft = 256
+    while ft > 64 and (ft > check_ft or ncols % ft):
+        ft //= 2
+    nsub, per = 256 // ft, max(1, check_per)
+    if n > 0 and min_blocks > 0:
+        per = max(1, min(per, n * (ncols // ft) // (min_blocks * nsub)))
+    return ft, per * nsub
+
+
+def assert_high_conditions(case, variant):
+    """Conditions on the frames of a high-degree case, from the oracle alone (before any GPU
+    output), at 30 iterations: some frames succeed and some fail, the successful ones stop at
+    >= 5 distinct iterations >= 1, the planted codewords stop at (1, 0), and at most 384 frames
+    still run after iteration 29, so at least one 128-column tile goes idle while the
+    active-frame lists are live.  Returns (successes, distinct stop iterations, still running)."""
+    succ, its, _ = oracle_of(case, MI)
+    n = int((succ != 0).sum())
+    assert 0 < n < LD, n
+    stops = np.unique(its[(succ != 0) & (its >= 1)])
+    assert stops.size >= 5, stops
+    if variant == "special":
+        cw = np.array(PLANTED[:8])
+        assert (succ[cw] == 1).all() and (its[cw] == 0).all(), (succ[cw], its[cw])
+    left = sum(running(succ, its, LD, MI - 1))
+    assert left <= 384, left
+    return n, int(stops.size), left
+
+
+# ------------------------------------------------------------------ the reference's own records
+# tests/golden/decoder_degrees.npz (tests/golden/make_golden_degrees.py): what the compiled
+# reference's Decoder.decode returned for the frames of these cases, as digests
+GOLDEN_MIS = (1, 2, 3, MI)
+CANON_NAN = 0x7FF8000000000000
+
+
+def _canon_bytes(a):
+    """The doubles' little-endian int64 view with every NaN replaced by CANON_NAN, as bytes."""
+    a = np.ascontiguousarray(a, np.float64)
+    bits = a.view(np.int64).copy()
+    bits[np.isnan(a)] = CANON_NAN
+    return bits.astype("<i8").tobytes()
+
+
+def frame_digests(final):
+    """[n, 8] uint8: per frame (row) the 8-byte BLAKE2b digest of its canonical bytes."""
+    final = np.ascontiguousarray(final, np.float64)
+    assert final.ndim == 2
+    return np.array([np.frombuffer(hashlib.blake2b(_canon_bytes(r), digest_size=8).digest(), np.uint8) for r in final],
+                    np.uint8).reshape(len(final), 8)
+
+
+def input_digest(llr, synd):
+    """[8] uint8: the digest of a case's inputs (shapes, canonical LAPPRs, syndromes)."""
+    h = hashlib.blake2b(digest_size=8)
+    h.update(np.array(llr.shape + synd.shape, "<i8").tobytes())
+    h.update(_canon_bytes(llr))
+    h.update(np.ascontiguousarray(synd, np.uint8).tobytes())
+    return np.frombuffer(h.digest(), np.uint8).copy()
+
+
+def golden_cases():
+    """name -> function returning the case, in the fixture's order: the degree matrix's and the
+    high degrees' cases, the repack file's small codes (special variant), the few-frame mixed
+    code, the high-degree mixed code."""
+    import few_fixture
+
+    cases = {}
+    for D in tuple(range(2, 17)) + HIGH_DEGREES:
+        for variant in ("clean", "special"):
+            cases[f"deg{D}-{variant}"] = functools.partial(case_of, D, variant)
+    for name in CODES:
+        cases[f"small-{name}-special"] = functools.partial(small_case, name, "special")
+    cases["few-mixed"] = few_fixture.mixed_case
+    for variant in ("clean", "special"):
+        cases[f"himix-{variant}"] = functools.partial(himix_case, variant)
+    return cases
+
+
+def golden_frames(n, mi):
+    """The frames of an n-frame case recorded at max_iterations = mi: all at 30; at 1, 2, 3 the
+    first 64 and every planted frame."""
+    if mi == MI:
+        return np.arange(n)
+    return np.array(sorted(set(range(min(n, 64))) | {f for f in PLANTED if f < n}))
+
+
+def golden_full_frames(n):
+    """The frames whose final LAPPRs at 30 iterations are recorded in full: the two that carry
+    special values and frame 12 (a 5-frame case: all)."""
+    return np.array([f for f in (8, 300, 12) if f < n] if n > 12 else range(n))
+
+
+class GoldenDegrees:
+    """Reader of tests/golden/decoder_degrees.npz: per case name the input digest, per
+    max_iterations of GOLDEN_MIS (frames, success, iterations, digests), and the full frames."""
+
+    def __init__(self, z):
+        self.names = [str(s) for s in z["names"]]
+        self.z = {k: z[k] for k in z.files}
+        self.at = {s: k for k, s in enumerate(self.names)}
+
+    def _part(self, key, name):
+        off = self.z[key + "_off"]
+        k = self.at[name]
+        return slice(int(off[k]), int(off[k + 1]))
+
+    def n_frames(self, name):
+        return int(self.z["n_frames"][self.at[name]])
+
+    def input_digest(self, name):
+        return self.z["input_digest"][self.at[name]]
+
+    def records(self, name, mi):
+        """(frames, success, iterations, digests [n, 8]) the reference returned at mi."""
+        p = self._part(f"mi{mi}", name)
+        frames = golden_frames(self.n_frames(name), mi)
+        assert p.stop - p.start == frames.size
+        return frames, self.z[f"mi{mi}_success"][p], self.z[f"mi{mi}_iters"][p], self.z[f"mi{mi}_digest"][p]
+
+    def full(self, name):
+        """(frames, final LAPPRs [k, V]) at 30 iterations."""
+        frames = golden_full_frames(self.n_frames(name))
+        p = self._part("full", name)
+        return frames, self.z["full"][p].reshape(frames.size, -1)
+
+
+def assert_golden_inputs(gold, name, case):
+    """The fixture was recorded on exactly these frames (detects generator drift first)."""
+    assert gold.n_frames(name) == case["llr"].shape[0], name
+    assert np.array_equal(gold.input_digest(name), input_digest(case["llr"], case["synd"])), \
+        f"{name}: the inputs differ from those tests/golden/make_golden_degrees.py recorded"
+
+
+def assert_golden_records(gold, name, mi, succ, its, final, tag=None):
+    """success, iterations and per-frame digests of final ([n, V], all frames of the case) equal
+    the reference's records at mi; the first differing frame is named."""
+    frames, s, i, d = gold.records(name, mi)
+    tag = tag or (name, mi)
+    assert np.array_equal(np.asarray(succ)[frames], s), (tag, "success", frames[np.asarray(succ)[frames] != s][:8])
+    assert np.array_equal(np.asarray(its)[frames], i), (tag, "iterations", frames[np.asarray(its)[frames] != i][:8])
+    bad = (frame_digests(np.asarray(final)[frames]) != d).any(axis=1)
+    assert not bad.any(), (tag, f"{int(bad.sum())} frames' final LAPPRs differ from the reference's; first",
+                           frames[bad][:8])
+
+
 # ------------------------------------------------------------------ graph builders
 def deal_sockets(dv, dc, rng):
     """(vid, cid): variable v has dv[v] sockets; the sockets are shuffled and dealt dc per check
@@ -308,6 +521,26 @@ def deal_sockets(dv, dc, rng):
     M = sockets.size // dc
     sockets = sockets[rng.permutation(sockets.size)][:M * dc]
     return sockets.astype(np.int64), np.repeat(np.arange(M), dc).astype(np.int64)
+
+
+def hub_code(V, classes, hub_degree, seed):
+    """(vid, cid): variable 0 is a hub of hub_degree sockets, every sixth variable (v % 6 == 2) is
+    isolated, every other one has 3 or 4 sockets; the sockets are shuffled by default_rng(seed)
+    and dealt check-major (parallel edges kept) to the checks of ``classes`` ((degree, number of
+    checks)) in a shuffled order."""
+    rng = np.random.default_rng(seed)
+    E = sum(d * n for d, n in classes)
+    conn = np.array([v for v in range(1, V) if v % 6 != 2])
+    extra = E - hub_degree - 3 * conn.size
+    assert 0 <= extra <= conn.size
+    deg = np.full(conn.size, 3)
+    deg[rng.permutation(conn.size)[:extra]] = 4
+    s = np.concatenate([np.zeros(hub_degree, np.int64), np.repeat(conn, deg)])
+    rng.shuffle(s)
+    degs = np.concatenate([np.full(n, d) for d, n in classes])
+    rng.shuffle(degs)
+    assert degs.sum() == s.size == E
+    return s.astype(np.int64), np.repeat(np.arange(degs.size), degs).astype(np.int64)
 
 
 def scattered_code(rng, deg, V):

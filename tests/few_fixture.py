@@ -35,19 +35,7 @@ MIXED_SIGMA = (0.55, 0.95)
 def mixed_code():
     """(vid, cid): the sockets (hub x 70, every other connected variable x 3 or 4) shuffled by
     default_rng(seed) and dealt check-major to the classes' checks in a shuffled order."""
-    rng = np.random.default_rng(MIXED_SEED)
-    E = sum(d * n for d, n in MIXED_CLASSES)
-    conn = np.array([v for v in range(1, MIXED_V) if v % 6 != 2])
-    extra = E - MIXED_HUB_DEGREE - 3 * conn.size
-    assert 0 <= extra <= conn.size
-    deg = np.full(conn.size, 3)
-    deg[rng.permutation(conn.size)[:extra]] = 4
-    s = np.concatenate([np.zeros(MIXED_HUB_DEGREE, np.int64), np.repeat(conn, deg)])
-    rng.shuffle(s)
-    degs = np.concatenate([np.full(n, d) for d, n in MIXED_CLASSES])
-    rng.shuffle(degs)
-    assert degs.sum() == s.size == E
-    return s.astype(np.int64), np.repeat(np.arange(degs.size), degs).astype(np.int64)
+    return DF.hub_code(MIXED_V, MIXED_CLASSES, MIXED_HUB_DEGREE, MIXED_SEED)
 
 
 def mixed_isolated():

@@ -2,14 +2,22 @@
 per check): degrees above the templated range (2..16) run the runtime-degree kernel
 with the forward values parked in an HBM scratch (decoder.hip k_check_generic).  Bit
 for bit against the oracle for degrees 17, 33, 65, 100 (and 255 on a small code), in
-every schedule, plus the node-level surface process_check_node on such checks."""
+every schedule, plus the node-level surface process_check_node on such checks.
+
+What runs here: single checks of degree 17, 33, 65, 100 among low-degree ones (V = 300, B = 70, ld = 128)
+with knob split 1 and 3; a code of runtime-degree classes only, one check of degree 255 (B = ld = 64);
+process_check_node on finite messages; the workspace's closed form (no kernel).  The matrix of the
+runtime-degree kernel -- whole classes of degrees 17 .. 255 at ld = 512, every knob that shapes its
+launch, max_iterations 0 .. 30, special values, ragged batches, few frames, graph capture, the node
+surface on special values, and the comparison with the compiled reference's own records -- is
+tests/test_gpu_high_degrees.py."""
 import numpy as np
 import pytest
 
 from conftest import assert_bit_exact
 
 import oracle as O
-from decode_fixture import knobs, scattered_code
+from decode_fixture import himix_code, knobs, scattered_code
 
 pytestmark = pytest.mark.gpu
 
@@ -73,14 +81,17 @@ def test_workspace_bytes_closed_form(gpu):
     from qamr import codes
 
     high = _high_degree_code(np.random.default_rng(17))
-    cases = [(codes.regular_code(1008), 64), (codes.regular_code(1008), 512), (high, 128)]
+    mixed = himix_code()   # classes of degrees 7, 12, 17, 30, 64: 65 * 15 + 13 * 28 + 62 F rows
+    cases = [(codes.regular_code(1008), 64), (codes.regular_code(1008), 512), (high, 128), (mixed, 512), (mixed, 64)]
     for repack in (1, 0):
         with knobs(repack=repack):
             for (vid, cid), ld in cases:
                 dec = qamr.Decoder(vid, cid)
                 for max_it in (0, 30):
                     want, fb_rows, iter_code = _workspace_closed_form(vid, cid, ld, max_it, repack)
-                    assert (fb_rows > 0) == (vid is high[0]) and iter_code == (vid is not high[0])
+                    runtime = vid is high[0] or vid is mixed[0]
+                    assert (fb_rows > 0) == runtime and iter_code == (not runtime)
+                    assert fb_rows == 65 * 15 + 13 * 28 + 62 or vid is not mixed[0]
                     assert dec.workspace_bytes(ld, max_it) == want, (vid.size, ld, max_it, repack)
 
 
