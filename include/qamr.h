@@ -46,9 +46,11 @@ extern "C" {
 #define QR_EMEMORY 2     /* -> MemoryError */
 #define QR_EDEVICE 3     /* HIP runtime error -> RuntimeError */
 #define QR_EUNSUPPORTED 4
+#define QR_EINTERNAL 5   /* a bounded retry ran out (qr_npstream_frames_device) -> RuntimeError */
 
 typedef struct qr_code qr_code;   /* Tanner graph resident in HBM   */
 typedef struct qr_demap qr_demap; /* NoiseMapper tables in HBM      */
+typedef struct qr_npstream qr_npstream; /* numpy's legacy global stream (MT19937 state + cached normal) */
 
 /* ------------------------------------------------------------------ misc */
 QR_API const char *qr_last_error(void);
@@ -66,7 +68,8 @@ QR_API int qr_profile_select(const char *names);
 /* name: "check" (one check sweep, all degree classes), "check_d<D>" (the launch
  * for check degree D), "check1" (first sweep), "var", "var_init", "status",
  * "parity", "demap", "demap_interp", "bob", "syndrome", "count"; the few-frame schedule:
- * "few_check" (every check-sweep launch), "few_var", "few_var_init".  Synchronises pending events. */
+ * "few_check" (every check-sweep launch), "few_var", "few_var_init"; numpy's stream: "np_words",
+ * "np_scan", "np_chain", "np_fill".  Synchronises pending events. */
 QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launches);
 
 /* Kernel-geometry knobs (process-wide; performance only, results unchanged):
@@ -84,7 +87,9 @@ QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launche
  * rebuilds a grid made under another value), "resident" (1 = small single-degree codes decode
  * frame-resident in LDS, one launch per decode), "few_max" (qr_decode_frames_device and
  * qr_decode_host decode up to this many frames with the few-frame schedule; 0..64, 0 = off, any
- * other value is QR_EVALUE and changes nothing). */
+ * other value is QR_EVALUE and changes nothing), "np_slack_pct" (qr_npstream_*: percent of the
+ * slack that the first generated range of a call gets past its mean, default 100; 0 = the mean
+ * alone, so about every other call tops up). */
 QR_API int qr_tune_set(const char *name, int64_t value);
 QR_API int qr_tune_get(const char *name, int64_t *value);
 
@@ -405,6 +410,50 @@ QR_API int qr_bsc_llr_device(double coef, double rber, int32_t B, int32_t ld, in
 QR_API int qr_count_errors_neg_device(int32_t B, int32_t ld, int64_t K, const double *d_final, const uint8_t *d_word,
                                       const uint8_t *d_success, const int32_t *d_iters, int32_t *d_frame_errors,
                                       int64_t *d_counters, void *stream);
+
+/* ---------------------------------------------------------- numpy's stream */
+/* numpy's legacy global stream (np.random.seed / get_state: MT19937, random_sample, choice with p,
+ * the polar legacy_gauss) continued on the GPU, bit for bit and in numpy's consumption order.  The
+ * state is np.random.get_state()'s: key[624] (the untempered current block), pos (0..624; 624 =
+ * regenerate before the next word), has_gauss and the cached normal.  Every call below draws from
+ * the handle's state and moves it; each one SYNCHRONISES the host with `stream` (the state after a
+ * call is read back from the device) and therefore cannot be captured into a graph.  Calls on one
+ * handle are serialised.  QR_EVALUE for null pointers and negative counts; a count of 0 is QR_OK
+ * and draws nothing. */
+QR_API int qr_npstream_create(const uint32_t *key, int32_t pos, int32_t has_gauss, double gauss, int32_t device,
+                              qr_npstream **out);
+QR_API int qr_npstream_destroy(qr_npstream *st);
+/* The current state; any output pointer may be null.  gauss is 0.0 when has_gauss is 0. */
+QR_API int qr_npstream_state(const qr_npstream *st, uint32_t *key, int32_t *pos, int32_t *has_gauss, double *gauss);
+/* d_out[n]: the next n words (np.random.bytes(4n) as '<u4'), the next n doubles
+ * (np.random.random_sample(n), two words each), the next n normals (np.random.randn(n): the cached
+ * value first when has_gauss; an odd count leaves one cached), the next n symbols
+ * (np.random.choice(M, size=n, p=p) with d_cdf[M] = p.cumsum() / p.cumsum()[-1] formed by the
+ * caller in numpy: the count of d_cdf[k] <= u; the cache is not touched; 2 <= M <= 256). */
+QR_API int qr_npstream_words_device(qr_npstream *st, int64_t n, uint32_t *d_out, void *stream);
+QR_API int qr_npstream_random_sample_device(qr_npstream *st, int64_t n, double *d_out, void *stream);
+QR_API int qr_npstream_standard_normal_device(qr_npstream *st, int64_t n, double *d_out, void *stream);
+QR_API int qr_npstream_choice_device(qr_npstream *st, int64_t n, int32_t M, const double *d_cdf, int64_t *d_out,
+                                     void *stream);
+/* B frames of sims/reconciliation.pyx:129-132 in sequence, frame f in column f: per frame
+ * x = np.random.choice(M, size=S, p=p), then y = a[x] + sigma * np.random.randn(S) (the product
+ * first, then the sum).  d_x int64 [S][ld], d_y float64 [S][ld], columns B..ld-1 written as zeros;
+ * d_frame_words int64 [B]: the words consumed through frame f, cumulative.  The workspace (256-byte
+ * aligned, qr_npstream_frames_workspace_size bytes, linear in B * S: about 28 bytes per symbol)
+ * holds the generated words, and qr_npstream_seek_frame reads it: keep it unchanged until the seek.
+ * The first generated range is the mean consumption plus a slack ("np_slack_pct"); when the frames
+ * need more, the range is extended and the frames are located again, at most 8 times, then
+ * QR_EINTERNAL.  QR_EVALUE before any launch for a null pointer, B <= 0, ld % 64 != 0, ld < B,
+ * S <= 0, M outside 2..256, a short or misaligned workspace, or B * S past 2^31 candidate pairs
+ * (split the batch). */
+QR_API int qr_npstream_frames_workspace_size(int64_t S, int32_t B, size_t *bytes);
+QR_API int qr_npstream_frames_device(qr_npstream *st, int32_t B, int32_t ld, int64_t S, int32_t M, const double *d_cdf,
+                                     const double *d_constellation, double sigma, int64_t *d_x, double *d_y,
+                                     int64_t *d_frame_words, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The state becomes the one after frame w (0-based) of the last qr_npstream_frames_device call on
+ * this handle: where a sequential loop that stopped after that frame leaves numpy.  QR_EVALUE when
+ * w is no frame of it or another draw was made since. */
+QR_API int qr_npstream_seek_frame(qr_npstream *st, int32_t w);
 
 /* --------------------------------------------------------- layout helpers */
 /* Frame-major [B][n] <-> frame-innermost [n][ld] transposes on the device. */

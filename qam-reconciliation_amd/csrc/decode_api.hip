@@ -196,7 +196,7 @@ static std::atomic<int> *tune_knob(const char *name) {
         {"fused_iter", &g_tune.fused_iter}, {"iter_streams", &g_tune.iter_streams},
         {"resident", &g_tune.resident},   {"repack", &g_tune.repack},
         {"repack_pct", &g_tune.repack_pct}, {"repack_grid", &g_tune.repack_grid},
-        {"few_max", &g_tune.few_max},
+        {"few_max", &g_tune.few_max},     {"np_slack_pct", &g_np_slack_pct},
     };
     const std::string n = name ? name : "";
     for (const auto &k : knobs)

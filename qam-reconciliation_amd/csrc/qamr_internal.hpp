@@ -104,6 +104,7 @@ extern std::atomic<int> g_demap_fast;  // demap.hip (tuning knob "demap_fast")
 extern std::atomic<int> g_demap_hyp;   // demap.hip (tuning knob "demap_hyp")
 extern std::atomic<int> g_interp_fast; // demap_interp.hip (tuning knob "interp_fast")
 extern std::atomic<int> g_interp_seg;  // demap_interp.hip (tuning knob "interp_seg")
+extern std::atomic<int> g_np_slack_pct; // npstream.hip (tuning knob "np_slack_pct")
 
 // Host helpers shared by demap.hip, demap_interp.hip, mi.hip and binary_channel.hip.
 int check_shape(int B, int ld, int64_t S);                // demap.hip: 0 < B <= ld, ld % 64 == 0, S > 0

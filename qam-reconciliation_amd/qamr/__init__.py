@@ -13,8 +13,9 @@ from .alphabet import Alphabet, PAMAlphabet, generate_table_s_to_b
 from .decoder import Decoder
 from .matrix import Matrix
 from .noisemapper import NoiseDemapper, NoiseMapper
+from .npstream import NumpyStream
 from .utils import count_errors_from_lappr
 
 __all__ = ["Decoder", "Matrix", "NoiseMapper", "NoiseDemapper", "PAMAlphabet", "Alphabet", "codes",
            "count_errors_from_lappr", "generate_table_s_to_b", "build", "load", "device_count", "QamrError",
-           "profile_enable", "profile_query", "profile_reset", "profile_select"]
+           "profile_enable", "profile_query", "profile_reset", "profile_select", "NumpyStream"]

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QAMR_LIB") or os.path.join(_HERE, "libqamr.so")
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 
-QR_OK, QR_EVALUE, QR_EMEMORY, QR_EDEVICE, QR_EUNSUPPORTED = 0, 1, 2, 3, 4
+QR_OK, QR_EVALUE, QR_EMEMORY, QR_EDEVICE, QR_EUNSUPPORTED, QR_EINTERNAL = 0, 1, 2, 3, 4, 5
 
 _lib = None
 
@@ -83,6 +83,16 @@ SIGNATURES = {
     "qr_biawgn_llr_device": [i32, f64, f64, i32, i32, i64, vp, vp, vp, vp],
     "qr_bsc_llr_device": [f64, f64, i32, i32, i64, vp, vp, vp, vp, vp],
     "qr_count_errors_neg_device": [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp],
+    "qr_npstream_create": [vp, i32, i32, f64, i32, P(vp)],
+    "qr_npstream_destroy": [vp],
+    "qr_npstream_state": [vp, vp, P(i32), P(i32), P(f64)],
+    "qr_npstream_words_device": [vp, i64, vp, vp],
+    "qr_npstream_random_sample_device": [vp, i64, vp, vp],
+    "qr_npstream_standard_normal_device": [vp, i64, vp, vp],
+    "qr_npstream_choice_device": [vp, i64, i32, vp, vp, vp],
+    "qr_npstream_frames_workspace_size": [i64, i32, P(C.c_size_t)],
+    "qr_npstream_frames_device": [vp, i32, i32, i64, i32, vp, vp, f64, vp, vp, vp, vp, C.c_size_t, vp],
+    "qr_npstream_seek_frame": [vp, i32],
     "qr_to_frame_innermost_f64": [i32, i32, i64, vp, vp, vp],
     "qr_to_frame_major_f64": [i32, i32, i64, vp, vp, vp],
     "qr_to_frame_innermost_u8": [i32, i32, i64, vp, vp, vp],

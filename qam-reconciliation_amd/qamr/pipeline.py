@@ -14,8 +14,9 @@ stage is one HIP kernel of libqamr:
   Alice  decode (k_check / k_status / k_var) :147
   count  BER/FER/iterations   (k_count_*)  :149-157
 
-The RNG stream is torch's, not numpy's: parity is established on the fixtures
-and the oracle, not on random streams.
+The RNG stream of this pipeline is torch's: its parity is established on the fixtures
+and the oracle.  The reference's own frames, drawn from numpy's legacy
+stream on the GPU, are the switch of the simulations: qamr.sim ``stream="numpy"`` (qamr.npstream).
 """
 from __future__ import annotations
 

@@ -16,7 +16,11 @@ error counts of every rank (``first_stop_frame``) and every counter is cut
 there, so the returned tuple is the one the reference's sequential loop
 returns for the same frames (tests/test_gpu_sim.py).  Returned tuples have the
 reference's shape: (snr_dB, ber, fer, average iterations of successful frames).
-RNG streams are torch's (per seed, rank and batch), not numpy's.
+RNG streams: ``stream="torch"`` (the default) draws every batch from torch's generator, seeded
+per seed, rank and batch; ``stream="numpy"`` draws the frames from numpy's legacy global stream on
+the GPU (qamr.npstream), frame after frame as the reference's loop does, so that after
+``np.random.seed(s)`` the returned tuple is the reference's and ``np.random.get_state()`` is left
+where the reference leaves it (one rank only: the frames of one stream are sequential).
 """
 from __future__ import annotations
 
@@ -34,12 +38,23 @@ from .pipeline import (alternating_config, check_demapper, count_errors_device, 
                        syndrome_device)
 
 MODES = ("softening", "direct", "hard")
+STREAMS = ("torch", "numpy")
+
+
+def check_stream(stream: str) -> str:
+    """The `stream` keyword of the simulations; numpy's stream is sequential, so it has no ranks."""
+    if stream not in STREAMS:
+        raise ValueError(f"stream must be one of {STREAMS}")
+    if stream == "numpy" and dist.env_world()[0] > 1:
+        raise ValueError('stream="numpy" runs on one rank: the frames of one stream are sequential')
+    return stream
 
 
 class Simulator:
     def __init__(self, decoder: Decoder, bps: int, mode: str = "softening", max_iterations: int = 50,
                  alpha: float = 1.0, batch: int = 4096, configuration_base: bool = False, step: float = 2.0,
-                 device: int = 0, demapper: str = "search"):
+                 device: int = 0, demapper: str = "search", stream: str = "torch"):
+        self.stream = check_stream(stream)
         self.demapper = check_demapper(demapper)   # softening mode only; the other modes have no soft demap
         import torch
 
@@ -82,14 +97,18 @@ class Simulator:
         return syndrome_device(self.dec, word, B, ld)
 
     def frames(self, nm: NoiseMapper, B: int, gen, two_variance: float):
-        """One batch of inputs for the selected mode: (lappr [V, ld], synd [C, ld], word [V, ld], ld)."""
+        """One batch of inputs for the selected mode: (lappr [V, ld], synd [C, ld], word [V, ld], ld).
+        gen: a torch generator, or the NumpyStream the frames are drawn from (stream="numpy")."""
         import torch
 
         ld = leading_dim(B)
         S = self.S
-        x = self._symbols(S, ld, gen)
-        y = self._a[x] + nm.noise_sigma * torch.randn((S, ld), generator=gen, device=self.device,
-                                                      dtype=torch.float64)
+        if self.stream == "numpy":                         # reconciliation.pyx:129-132, frame after frame
+            x, y, _ = gen.frames(self.pa.probabilities, self.pa.constellation, nm.noise_sigma, S, B, ld=ld)
+        else:
+            x = self._symbols(S, ld, gen)
+            y = self._a[x] + nm.noise_sigma * torch.randn((S, ld), generator=gen, device=self.device,
+                                                          dtype=torch.float64)
         lappr = torch.empty((self.V, ld), dtype=torch.float64, device=self.device)
         if self.mode == "softening":                       # reconciliation.pyx:129-145
             _, nhat, word = nm.bob_map_device(y, B)
@@ -129,15 +148,22 @@ class Simulator:
     def run_snr(self, snr_dB: float, simulation_loops: int, ferr_count_min: int, seed: int = 0, hook=None):
         """Frames until `simulation_loops` or the early stop; returns
         (snr_dB, ber, fer, avg_iterations_of_successes).  hook(batch_index, lappr, synd, word, B):
-        optional view of every shard's inputs (tests)."""
+        optional view of every shard's inputs (tests).  With stream="numpy" the frames come from
+        numpy's global stream, which is left after the last frame counted; `seed` is not read (the
+        caller seeds numpy, as for montecarlo_information)."""
         Es = self.pa.variance
         two_var = Es * (10 ** (-snr_dB / 10))          # reconciliation.pyx:191-192, 272-273
         N0 = Es * (10 ** (-snr_dB / 10)) / 2           # reconciliation.pyx:109-110
         cfg = self.cfg if self.mode == "softening" else None
         nm = NoiseMapper(self.pa, N0, cfg, device=self._dev_index)
 
-        be, fe, su, it, fr = run_seeded(lambda B, gen, h: self.batch_results(nm, B, gen, two_var, h), seed, hook,
-                                        self.batch, simulation_loops, ferr_count_min, self.device)
+        batch_fn = lambda B, gen, h: self.batch_results(nm, B, gen, two_var, h)   # noqa: E731
+        if self.stream == "numpy":
+            be, fe, su, it, fr = run_numpy_stream(batch_fn, hook, self.batch, simulation_loops, ferr_count_min,
+                                                  self.device)
+        else:
+            be, fe, su, it, fr = run_seeded(batch_fn, seed, hook, self.batch, simulation_loops, ferr_count_min,
+                                            self.device)
         return (snr_dB, be / (fr * self.K), fe / fr, 0 if su == 0 else it / su)
 
 
@@ -200,13 +226,14 @@ def first_stop_frame(prev_frame_errors: int, ferr, start: int, done: int, ferr_c
 
 
 def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int, device=None,
-               rule: StopRule | None = None):
+               rule: StopRule | None = None, on_stop=None):
     """The frame loop of reconciliation.pyx:127-168 over batches of batch * world frames,
     each rank taking its contiguous shard (dist.shard).  frame_fn(batch_index, start, B) ->
     (ferr, succ, its, delta) for this rank's B frames [done + start, done + start + B) of the
     batch (delta = their five counters).  Returns the five global counters at the reference's
     stopping frame: {bit_errors, frame_errors, successes, iteration_sum, frames = wordcount+1}.
-    `rule`: another monotone stopping rule in place of :159-161 (ferr_count_min is then not read)."""
+    `rule`: another monotone stopping rule in place of :159-161 (ferr_count_min is then not read).
+    on_stop(i): called when the loop stops early after frame i of this rank's shard of the batch."""
     import torch
 
     world, rank, _ = dist.env_world()
@@ -229,6 +256,8 @@ def run_frames(frame_fn, batch: int, simulation_loops: int, ferr_count_min: int,
             prev = int(total[1 if rule is None else rule.counter])
             g = first_stop_frame(prev, ferr, start, done, ferr_count_min, simulation_loops, rule)
             keep = min(max(g - (done + start) + 1, 0), B)
+            if on_stop is not None and keep:
+                on_stop(keep - 1)
             part = shard_counters(ferr, succ, its, keep) if keep else torch.zeros(5, dtype=torch.int64,
                                                                                  device=device)
             dist.all_reduce_sum(part)
@@ -257,23 +286,46 @@ def run_seeded(batch_fn, seed: int, hook, batch: int, simulation_loops: int, fer
     return run_frames(frame_fn, batch, simulation_loops, ferr_count_min, device, rule)
 
 
+def run_numpy_stream(batch_fn, hook, batch: int, simulation_loops: int, ferr_count_min: int, device,
+                     rule: StopRule | None = None):
+    """run_frames over batch_fn(B, stream, hook or None) with every batch drawn from one NumpyStream
+    that starts at numpy's global state.  When the loop stops early at a frame, the stream seeks to
+    that frame; in every case numpy's global state is committed at return, so np.random stands where
+    the reference's sequential loop leaves it."""
+    from .npstream import NumpyStream
+
+    check_stream("numpy")
+    ns = NumpyStream(device=device.index)
+
+    def frame_fn(bidx, start, B):
+        h = None if hook is None else (lambda l, s, w, b: hook(bidx, l, s, w, b))
+        return batch_fn(B, ns, h)
+
+    try:
+        return run_frames(frame_fn, batch, simulation_loops, ferr_count_min, device, rule, on_stop=ns.seek_frame)
+    finally:
+        ns.commit()
+
+
 def simulate_softening_snr_dB(snr_dB, dec, bps, nmconfig, decoder_iterations, simulation_loops, ferr_count_min,
-                              alpha=1.0, batch=4096, seed=0, demapper="search"):
+                              alpha=1.0, batch=4096, seed=0, demapper="search", stream="torch"):
     """reconciliation.pyx:93-168 (the Matrix is the decoder's own graph).  demapper="simplified"
-    swaps demap_lappr_array (:143) for demap_lappr_simplified_array."""
-    sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch, demapper=demapper)
+    swaps demap_lappr_array (:143) for demap_lappr_simplified_array.  stream="numpy": after
+    np.random.seed(s), the tuple the reference returns after that seed (`seed` is not read)."""
+    sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch, demapper=demapper, stream=stream)
     sim.cfg = np.ascontiguousarray(nmconfig, np.uint8)
     return sim.run_snr(snr_dB, simulation_loops, ferr_count_min, seed)
 
 
-def simulate_direct_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096, seed=0):
+def simulate_direct_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096, seed=0,
+                           stream="torch"):
     """reconciliation.pyx:173-249"""
-    return Simulator(dec, bps, "direct", decoder_iterations, 1.0, batch).run_snr(
+    return Simulator(dec, bps, "direct", decoder_iterations, 1.0, batch, stream=stream).run_snr(
         snr_dB, simulation_loops, ferr_count_min, seed)
 
 
 def simulate_hard_reverse_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096,
-                                 seed=0):
+                                 seed=0, stream="torch"):
     """reconciliation.pyx:253-329"""
-    return Simulator(dec, bps, "hard", decoder_iterations, 1.0, batch).run_snr(
+    return Simulator(dec, bps, "hard", decoder_iterations, 1.0, batch, stream=stream).run_snr(
         snr_dB, simulation_loops, ferr_count_min, seed)

@@ -7,7 +7,9 @@ draws a uniform word, takes its syndrome, forms the channel LLRs, decodes, and c
 whose final LAPPR is < 0 against the word.  Here a batch of B frames is drawn by torch, turned into
 LLRs by one libqamr kernel (csrc/binary_channel.hip), decoded and counted in HBM, sharded over the
 ranks and cut at the reference's stopping frame exactly as qamr.sim does (run_frames with the
-script's own stopping rule).  RNG streams are torch's (per seed, rank and batch), not numpy's.
+script's own stopping rule).  RNG streams are torch's (per seed, rank and batch); numpy's legacy
+stream on the GPU is the switch of qamr.sim alone (``stream="numpy"``: these scripts draw from
+np.random.default_rng, another generator).
 """
 from __future__ import annotations
 

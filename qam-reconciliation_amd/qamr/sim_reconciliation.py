@@ -4,7 +4,8 @@ CSV schema of sim_reconciliation.py:27-102, README.md:107-145).
     PYTHONPATH=qam-reconciliation_amd python -m qamr.sim_reconciliation EDGEFILE \\
         [--out out.csv] [--maxiter 50] [--ferr-count-min 100] [--alpha 1.0] \\
         [--simloops 5000] [--snr 0 5] [--nsnr 11] [--bps 2] [--hard | --direct] \\
-        [--configuration-base] [--batch 4096] [--seed 0] [--demapper {search,simplified}]
+        [--configuration-base] [--batch 4096] [--seed 0] [--demapper {search,simplified}] \\
+        [--stream {torch,numpy}]
 
 Instead of one OS process per SNR point (parfor), every SNR point runs batched
 on the GPU(s); launched under torchrun, each rank takes its share of every
@@ -38,6 +39,10 @@ def build_parser():
     p.add_argument("--demapper", choices=("search", "simplified"), default="search",
                    help="Soft demapper of the softening scheme: the g_inv_search one, or formulation 1 on the "
                         "interpolated g_inv")
+    p.add_argument("--stream", choices=("torch", "numpy"), default="torch",
+                   help="RNG stream of the frames: torch's generator (seeded per seed, rank and batch), or numpy's "
+                        "legacy global stream, seeded with --seed before every SNR point: each row is then what "
+                        "the reference's function returns after np.random.seed(seed) (one rank only)")
     return p
 
 
@@ -54,9 +59,12 @@ def main(argv=None):
     dec = Decoder(vid, cid, device=local)
     mode = "direct" if args.direct else ("hard" if args.hard else "softening")
     sim = Simulator(dec, args.bps, mode, args.maxiter, args.alpha, args.batch,
-                    configuration_base=args.configuration_base, device=local, demapper=args.demapper)
+                    configuration_base=args.configuration_base, device=local, demapper=args.demapper,
+                    stream=args.stream)
     rows = []
     for snr in np.linspace(args.snr[0], args.snr[1], args.nsnr):
+        if args.stream == "numpy":
+            np.random.seed(args.seed)
         rows.append(sim.run_snr(float(snr), args.simloops, args.ferr_count_min, args.seed))
         if rank == 0:
             print("EsN0dB=%.3f ber=%.6g fer=%.6g iters=%.3f" % rows[-1], flush=True)
