@@ -2,42 +2,27 @@
 qamr_math.hpp::g_inv_search_fast) is bit-identical to the reference search
 (noisemapper.pyx:310-345 restated as qamr_math.hpp::g_inv_search), compiled
 for the host with hipcc over random targets, orders, SNRs and sign configs."""
-import os
-import subprocess
-import sys
+import re
 
-import pytest
+import numpy as np
 
-from conftest import ROOT
+from conftest import golden
+
+from native_check import build, run
 
 
 def test_fast_search_bit_identical(tmp_path):
-    src = os.path.join(ROOT, "tests", "native", "replay_check.cpp")
-    exe = str(tmp_path / "replay_check")
-    csrc = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc unavailable")
-    subprocess.run([sys.executable, os.path.join(csrc, "gen_glibc_tables.py"), str(tmp_path / "glibc_tables.inc")],
-                   check=True)
-    cc = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
-                         "-I" + csrc, "-I" + str(tmp_path), "-o", exe, src], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-2000:]
-    run = subprocess.run([exe, "120000"], capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout
-    assert "mismatches=0" in run.stdout
+    out = run(build(tmp_path, "replay_check.cpp"), "120000", timeout=300)
+    assert "mismatches=0" in out
     # the fast path itself must be exercised: Newton certifies ~91 % of these draws (the rest
     # are the edge targets n = 0 / 1, 1e-12-deep tails and -2 dB spreads: brute force)
-    import re
-    m = re.search(r"draws=(\d+) mismatches=\d+ fallbacks=(\d+)", run.stdout)
-    assert m and int(m.group(2)) < 0.15 * int(m.group(1)), run.stdout
+    m = re.search(r"draws=(\d+) mismatches=\d+ fallbacks=(\d+)", out)
+    assert m and int(m.group(2)) < 0.15 * int(m.group(1)), out
 
 
 def _dump_wide_cases(path):
     """The constructor arguments of every demap_wide.npz case as text for replay_wide_check
     (hexadecimal floats: exact), with the alphabet tables of qamr.PAMAlphabet."""
-    import numpy as np
-    from conftest import golden
     from qamr import PAMAlphabet
 
     g = golden("demap_wide.npz")
@@ -56,27 +41,13 @@ def test_fast_search_bit_identical_wide(tmp_path):
     """replay_wide_check: g_inv_search_fast == g_inv_search on tables from the library's own
     build_demap_host, for every demap_wide.npz case and the grid bps 1..5 x {uniform, shaped} x
     {-12, 3, 25, 50, 70, 80} dB; the fixture cases reach all three regimes of the root search."""
-    import re
-
-    src = os.path.join(ROOT, "tests", "native", "replay_wide_check.cpp")
-    exe = str(tmp_path / "replay_wide_check")
-    csrc = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc unavailable")
-    subprocess.run([sys.executable, os.path.join(csrc, "gen_glibc_tables.py"), str(tmp_path / "glibc_tables.inc")],
-                   check=True)
-    cc = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
-                         "-I" + csrc, "-I" + str(tmp_path), "-I" + os.path.join(ROOT, "include"), "-o", exe, src],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-2000:]
+    exe = build(tmp_path, "replay_wide_check.cpp")
     n_cases = _dump_wide_cases(str(tmp_path / "cases.txt"))
-    run = subprocess.run([exe, "1500", str(tmp_path / "cases.txt")], capture_output=True, text=True, timeout=900)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout[-4000:]
+    out = run(exe, "1500", str(tmp_path / "cases.txt"), timeout=900)
     rows = [dict(label=m.group(1), **{k: float(v) for k, v in re.findall(r"(\w+)=([-\d.e+]+)", m.group(2))})
-            for m in re.finditer(r"^cfg (\S+) (.*)$", run.stdout, re.M)]
-    assert len(rows) == n_cases + 5 * 2 * 6, run.stdout[-4000:]
-    assert re.search(r"^total draws=\d+ mismatches=0 ", run.stdout, re.M), run.stdout[-4000:]
+            for m in re.finditer(r"^cfg (\S+) (.*)$", out, re.M)]
+    assert len(rows) == n_cases + 5 * 2 * 6, out[-4000:]
+    assert re.search(r"^total draws=\d+ mismatches=0 ", out, re.M), out[-4000:]
     assert all(r["mismatches"] == 0 for r in rows)
     # the three regimes build_demap_host chooses between, each met by a fixture case (the GPU
     # tests of tests/test_gpu_demap_wide.py run those cases)
@@ -98,17 +69,4 @@ def test_fast_search_bit_identical_wide(tmp_path):
 
 def test_llr_exponent_division_bit_identical(tmp_path):
     """qamr_math.hpp::div_two_s2 (reciprocal + FMA correction) == IEEE x / (2 sigma^2)."""
-    src = os.path.join(ROOT, "tests", "native", "division_check.cpp")
-    exe = str(tmp_path / "division_check")
-    csrc = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc unavailable")
-    subprocess.run([sys.executable, os.path.join(csrc, "gen_glibc_tables.py"), str(tmp_path / "glibc_tables.inc")],
-                   check=True)
-    cc = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
-                         "-I" + csrc, "-I" + str(tmp_path), "-o", exe, src], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-2000:]
-    run = subprocess.run([exe, "20000000"], capture_output=True, text=True, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout
-    assert "mismatches=0" in run.stdout
+    assert "mismatches=0" in run(build(tmp_path, "division_check.cpp"), "20000000", timeout=300)

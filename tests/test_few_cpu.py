@@ -1,7 +1,6 @@
 """CPU tests of the few-frame decode: the message-slot layout builder under sanitizers, the
 ``few_max`` knob, and the few-frame kernels in the built gfx950 code object."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -10,10 +9,9 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 import few_fixture as F
+import native_check
 
-CSRC = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
 LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr.so")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
 
 
 def test_few_layout_under_asan_ubsan(tmp_path):
@@ -24,9 +22,7 @@ def test_few_layout_under_asan_ubsan(tmp_path):
     regular_code(770, 3, 7)."""
     from qamr import codes
 
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc unavailable")
+    exe = native_check.build(tmp_path, "few_layout_check.cpp", opt="-O1", sanitize=True, extra=["-fno-fast-math"])
     cases = {"hamming": codes.load_edge_csv(os.path.join(GOLDEN, "hamming_7-4.csv")), "mixed": F.mixed_code(),
              "reg770": codes.regular_code(770, 3, 7)}
     vid, cid = cases["mixed"]
@@ -35,24 +31,7 @@ def test_few_layout_under_asan_ubsan(tmp_path):
     for name, (v, c) in cases.items():
         files.append(str(tmp_path / f"{name}.edges"))
         F.write_edges(files[-1], v, c)
-    subprocess.run([sys.executable, os.path.join(CSRC, "gen_glibc_tables.py"), str(tmp_path / "glibc_tables.inc")],
-                   check=True)
-    exe = str(tmp_path / "few_layout_check")
-    san = []
-    for f in ("-fsanitize=address", "-fsanitize=undefined", "-fno-sanitize-recover=all"):
-        san += ["-Xarch_host", f]
-    cc = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                         "-fno-fast-math", "-fno-omit-frame-pointer", *san, "-I" + CSRC, "-I" + str(tmp_path),
-                         "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                         os.path.join(ROOT, "tests", "native", "few_layout_check.cpp")],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    r = subprocess.run([exe, *files], capture_output=True, text=True, timeout=600, env=ENV)
-    out = r.stdout + r.stderr
-    print(out[-3000:])
-    assert r.returncode == 0, out[-3000:]
-    assert "runtime error" not in out and "AddressSanitizer" not in out
-    assert "few_layout_check ok: 3 codes" in out
+    assert "few_layout_check ok: 3 codes" in native_check.run(exe, *files)
 
 
 def test_few_max_knob():

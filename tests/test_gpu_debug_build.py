@@ -14,16 +14,11 @@ of codes past one pass of its 512 threads and with isolated variables, the repac
 variable degrees (tests/test_gpu_resident_shapes.py) and three entries of the degree matrix
 (tests/test_gpu_degree_matrix.py: narrow sweeps of degrees 8 and 2, unpacked degree 15) in a child
 process on that library; conftest's autouse fixture fails any test after which a device check failed."""
-import os
-import subprocess
-import sys
-
 import pytest
 
-pytestmark = pytest.mark.gpu
+from debug_rerun import rerun_on_debug_build
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-DEBUG_LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr_debug.so")
+pytestmark = pytest.mark.gpu
 
 CASES = [
     "tests/test_gpu_timed_schedule.py::test_column_repack_vs_oracle[2-4.0-4096-50]",
@@ -52,10 +47,4 @@ CASES = [
 
 
 def test_debug_build_device_checks(gpu):
-    assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
-    env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", *CASES], cwd=ROOT,
-                       env=env, capture_output=True, text=True, timeout=900)
-    tail = (r.stdout + r.stderr)[-3000:]
-    assert r.returncode == 0, tail
-    assert "23 passed" in r.stdout, tail  # the 20 cases above (the batch-shape test has 4 parameters)
+    rerun_on_debug_build(CASES, 23, timeout=900)  # the 20 cases above (the batch-shape test has 4 parameters)

@@ -6,8 +6,6 @@ build_demap_host drops the Taylor table and Newton runs on the component sums.  
 the root search each case reaches is reported and asserted on the host by
 tests/test_demap_replay.py::test_fast_search_bit_identical_wide.  Everything is bit for bit
 (conftest.assert_bit_exact: infinities and the NaN pattern included)."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -15,6 +13,7 @@ from conftest import assert_bit_exact, golden
 
 import oracle as O
 from decode_fixture import knobs
+from mapper_fixture import FIXTURE, block_expected, mapper
 
 import make_golden_cases as MC
 
@@ -30,14 +29,13 @@ SETTINGS = {"wave_private": (1, 1),   # k_demap_wave for bps <= 6; bps 7, 8 fall
             "brute_force": (1, 0)}    # k_demap<false, .>: the reference's loops verbatim
 
 
-@functools.lru_cache(maxsize=None)
+_NM = {}
+
+
 def _nm(c, base):
-    """The case's NoiseMapper (built once: its host tables cost more than the kernels here)."""
-    import qamr
-    g = golden("demap_wide.npz")
-    k = f"c{c}_"
-    return qamr.NoiseMapper(qamr.PAMAlphabet(int(g[k + "bps"]), 2.0, g[k + "probs"]), float(g[k + "noise_var"]),
-                            None if base else g[k + "cfg"])
+    """The case's NoiseMapper (built once: its host tables cost more than the kernels here); base: with
+    NoiseMapper's default sign configuration instead of the case's."""
+    return mapper(golden("demap_wide.npz"), f"c{c}_", None if base else FIXTURE, cache=_NM)[1]
 
 
 def _padded_block(n, j, M, ld):
@@ -97,9 +95,7 @@ def test_device_entry_vs_reference(gpu, c, setting):
     hyp, fast = SETTINGS[setting]
     with knobs(demap_hyp=hyp, demap_fast=fast):
         got = _device_demap(nm, n, j, ALPHA)
-    # la[(s * B + f) * bps + k] -> row s * bps + k, column f
-    ref = (g[k + "la"] * ALPHA).reshape(S, B, bps).transpose(0, 2, 1).reshape(S * bps, B)
-    assert_bit_exact(got, ref)
+    assert_bit_exact(got, block_expected(g[k + "la"] * ALPHA, S, B, bps))
 
 
 @pytest.mark.parametrize("c", range(N_CASES))

@@ -4,16 +4,11 @@ message slot (check and variable sweeps) and the lane -> (class, check) mapping 
 DebugSite 17..19).  A child process on that library runs the mixed-class, routing, sizing and
 graph-capture tests of tests/test_gpu_few_frames.py and degrees 2, 8 and 15 of its degree matrix;
 conftest's autouse fixture fails any test after which a device check failed."""
-import os
-import subprocess
-import sys
-
 import pytest
 
-pytestmark = pytest.mark.gpu
+from debug_rerun import rerun_on_debug_build
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-DEBUG_LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr_debug.so")
+pytestmark = pytest.mark.gpu
 
 FILE = "tests/test_gpu_few_frames.py"
 CASES = [
@@ -31,10 +26,4 @@ CASES = [
 
 
 def test_few_frames_debug_build_device_checks(gpu):
-    assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
-    env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", *CASES], cwd=ROOT,
-                       env=env, capture_output=True, text=True, timeout=300)
-    tail = (r.stdout + r.stderr)[-3000:]
-    assert r.returncode == 0, tail
-    assert "11 passed" in r.stdout, tail  # the 10 entries above (the mixed-class test has 2 parameters)
+    rerun_on_debug_build(CASES, 11, timeout=300)  # the 10 entries above (the mixed-class test has 2 parameters)

@@ -6,21 +6,18 @@ noisemapper.pyx:27-63, 135-144, 295-307, 391-403, 563-620).  Every comparison is
 grid index search (knob interp_fast 1 = coarse table + segment bisection, 0 = the reference's
 __binsearch probe for probe) and across coarse-table segment sizes (knob interp_seg)."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bit_exact, golden
+from conftest import assert_bit_exact, golden
 
+from debug_rerun import rerun_on_debug_build
 from decode_fixture import knobs
+from mapper_fixture import block_expected, mapper, sha, to_dev
 
 pytestmark = pytest.mark.gpu
 
-DEBUG_LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr_debug.so")
 N_CASES = 11   # interp.npz "n_cases" (checked in test_interp_cpu.py)
 WAVE_CASES = list(range(N_CASES))   # every fixture case has bps <= 6: the batched kernel serves it
 
@@ -33,31 +30,8 @@ def fx():
 
 
 def make_nm(g, c):
-    import qamr
-
-    k = f"c{c}_"
-    probs = g[k + "probs"]
-    pa = qamr.PAMAlphabet(int(g[k + "bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-    return qamr.NoiseMapper(pa, float(g[k + "noise_var"]), g[k + "cfg"], float(g[k + "trunc"]), int(g[k + "nips"]))
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a, np.float64).tobytes()).hexdigest()
-
-
-def block_expected(la, S, B, bps):
-    """[S * B * bps] symbol-major LAPPRs -> the decoder's layout [S * bps][B] (v = s * bps + k)."""
-    return np.ascontiguousarray(la.reshape(S, B, bps).transpose(0, 2, 1).reshape(S * bps, B))
-
-
-def to_dev(a, ld, dtype):
-    """Host [S][B] -> device [S][ld], padding columns zero."""
-    import torch
-
-    S, B = a.shape
-    t = torch.zeros((S, ld), dtype=dtype, device="cuda")
-    t[:, :B] = torch.from_numpy(np.ascontiguousarray(a)).to("cuda").to(dtype)
-    return t
+    """A new NoiseMapper in every test: knob interp_seg is read when its grid is built."""
+    return mapper(g, f"c{c}_")[1]
 
 
 # ----------------------------------------------------------------------- grid
@@ -387,11 +361,4 @@ def test_debug_build_interp_index_checks(gpu):
     """This file's parity tests in a child process on libqamr_debug.so: the grid index checks
     (0 <= r, r + 1 < n_points where pair r + 1 is read, the coarse-table index; grid_interp.hpp QR_DCHECK)
     never fail -- conftest's autouse fixture fails any test after which one did."""
-    assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
-    env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
-                        *[f"tests/test_gpu_interp.py::{t}" for t in PARITY]], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-3000:]
-    assert r.returncode == 0, tail
-    assert f"{len(PARITY)} passed" in r.stdout, tail
+    rerun_on_debug_build([f"tests/test_gpu_interp.py::{t}" for t in PARITY], len(PARITY), timeout=600)

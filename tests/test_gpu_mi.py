@@ -4,18 +4,17 @@ lines of mutual_information.pyx:245-297).  Every comparison is bit for bit (conf
 infinities compare as bits, NaN matches NaN)."""
 import ctypes as C
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bit_exact, golden
+from conftest import assert_bit_exact, golden
+
+from debug_rerun import rerun_on_debug_build
+from mapper_fixture import expected_terms, mapper, mc_inputs, run_device
 
 pytestmark = pytest.mark.gpu
 
-DEBUG_LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr_debug.so")
 CASES = list(range(1, 9))
 B, S, LD = 70, 37, 128
 
@@ -25,43 +24,6 @@ def fx():
     g = golden("mi.npz")
     assert int(g["n_cases"]) == 8 and int(g["B"]) == B and int(g["S"]) == S
     return g
-
-
-def make_nm(g, c):
-    import qamr
-
-    k = f"c{c}_"
-    probs = g[k + "probs"]
-    pa = qamr.PAMAlphabet(int(g[k + "bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-    return pa, qamr.NoiseMapper(pa, float(g[k + "noise_var"]), g[k + "cfg"])
-
-
-def to_dev(a, ld, dtype):
-    """Host [B][S] (block-major, as stored) -> device [S][ld] frame-innermost, padding columns zero."""
-    import torch
-
-    a = np.ascontiguousarray(np.asarray(a).T)
-    t = torch.zeros((a.shape[0], ld), dtype=dtype, device="cuda")
-    t[:, :a.shape[1]] = torch.from_numpy(a).to("cuda").to(dtype)
-    return t
-
-
-def run_device(nm, pX, x, y, nblk, ld, which=(1, 1, 1)):
-    """-> (info [3][ld], terms [3][S][ld]) as numpy, both pre-filled with NaN."""
-    import torch
-    from qamr.mutual_information import montecarlo_information_device
-
-    Sq = x.shape[0]
-    info = torch.full((3, ld), float("nan"), dtype=torch.float64, device="cuda")
-    terms = torch.full((3, Sq, ld), float("nan"), dtype=torch.float64, device="cuda")
-    ret, t = montecarlo_information_device(nm, pX, x, y, nblk, which=np.array(which, np.uint8), terms=terms, out=info)
-    torch.cuda.synchronize()
-    assert t.data_ptr() == terms.data_ptr() and ret.data_ptr() == info.data_ptr() and tuple(ret.shape) == (3, nblk)
-    return info.cpu().numpy(), terms.cpu().numpy()
-
-
-def expected_terms(g, c, nblk=B):
-    return np.ascontiguousarray(g[f"c{c}_terms"][:, :nblk, :].transpose(0, 2, 1))   # [3][S][B]
 
 
 def test_device_log2_vs_libm(gpu):
@@ -96,18 +58,17 @@ def test_device_blocks_vs_reference(gpu, fx, c):
     """The device entry at B = 70, ld = 128, S = 37 (two tiles, the second with 6 valid lanes): terms and
     totals equal the fixture's, the padding columns are not written, p_Xhat from the device's NoiseMapper
     equals the fixture's; then the same at B = 1, ld = 64."""
-    import torch
     from qamr.mutual_information import P_xhat, montecarlo_information_device, mutual_information_X_Xhat
 
-    pa, nm = make_nm(fx, c)
     k = f"c{c}_"
+    pa, nm = mapper(fx, k)
     pX = P_xhat(nm)
     assert_bit_exact(pX, fx[k + "p_Xhat"])
     assert_bit_exact(nm.fwrd_transition_probability, fx[k + "fwrd"])
     assert_bit_exact([mutual_information_X_Xhat(nm, pX)], [fx[k + "I_X_Xhat"]])
-    x, y = to_dev(fx[k + "x"].astype(np.int64), LD, torch.int64), to_dev(fx[k + "y"], LD, torch.float64)
+    x, y = mc_inputs(fx, k, LD)
     info, terms = run_device(nm, pX, x, y, B, LD)
-    assert_bit_exact(terms[:, :, :B], expected_terms(fx, c))
+    assert_bit_exact(terms[:, :, :B], expected_terms(fx, k))
     assert_bit_exact(info[:, :B], fx[k + "totals"].T)
     assert np.isnan(terms[:, :, B:]).all() and np.isnan(info[:, B:]).all()
     # without the terms (they live in the workspace) the totals are the same
@@ -115,9 +76,9 @@ def test_device_blocks_vs_reference(gpu, fx, c):
     assert tuple(plain.shape) == (3, B)
     assert_bit_exact(plain.cpu().numpy(), fx[k + "totals"].T)
     # one block, one tile
-    x1, y1 = to_dev(fx[k + "x"][:1].astype(np.int64), 64, torch.int64), to_dev(fx[k + "y"][:1], 64, torch.float64)
+    x1, y1 = mc_inputs(fx, k, 64, 1)
     info1, terms1 = run_device(nm, pX, x1, y1, 1, 64)
-    assert_bit_exact(terms1[:, :, :1], expected_terms(fx, c, 1))
+    assert_bit_exact(terms1[:, :, :1], expected_terms(fx, k, 1))
     assert_bit_exact(info1[:, 0], fx[k + "totals"][0])
     assert np.isnan(terms1[:, :, 1:]).all() and np.isnan(info1[:, 1:]).all()
 
@@ -125,15 +86,13 @@ def test_device_blocks_vs_reference(gpu, fx, c):
 def test_which_masks(gpu, fx):
     """All 8 masks on case 5: a disabled quantity is exactly 0.0 / N and its term plane is not written,
     the enabled ones are unchanged."""
-    import torch
     from qamr.mutual_information import P_xhat
 
-    c = 5
-    pa, nm = make_nm(fx, c)
+    k = "c5_"
+    pa, nm = mapper(fx, k)
     pX = P_xhat(nm)
-    k = f"c{c}_"
-    x, y = to_dev(fx[k + "x"].astype(np.int64), LD, torch.int64), to_dev(fx[k + "y"], LD, torch.float64)
-    exp_t, exp_i = expected_terms(fx, c), fx[k + "totals"].T
+    x, y = mc_inputs(fx, k, LD)
+    exp_t, exp_i = expected_terms(fx, k), fx[k + "totals"].T
     for mask in range(8):
         which = [(mask >> q) & 1 for q in range(3)]
         info, terms = run_device(nm, pX, x, y, B, LD, which)
@@ -155,9 +114,9 @@ def test_host_entry_and_montecarlo_information(gpu, fx, c):
     from qamr import _lib
     from qamr.mutual_information import P_xhat, montecarlo_information
 
-    pa, nm = make_nm(fx, c)
-    pX = P_xhat(nm)
     k = f"c{c}_"
+    pa, nm = mapper(fx, k)
+    pX = P_xhat(nm)
     for f in (0, 3, 69):
         np.random.seed(5000 + 100 * c + f)
         terms = np.full((3, S), np.nan)
@@ -185,18 +144,16 @@ def test_host_entry_and_montecarlo_information(gpu, fx, c):
 
 
 def test_out_of_range_symbol_is_nan_for_that_sample_only(gpu, fx):
-    import torch
     from qamr.mutual_information import P_xhat
 
-    c = 6
-    pa, nm = make_nm(fx, c)
+    k = "c6_"
+    pa, nm = mapper(fx, k)
     pX = P_xhat(nm)
-    k = f"c{c}_"
-    x, y = to_dev(fx[k + "x"].astype(np.int64), LD, torch.int64), to_dev(fx[k + "y"], LD, torch.float64)
+    x, y = mc_inputs(fx, k, LD)
     x[2, 5] = nm.order
     x[36, 69] = -1
     info, terms = run_device(nm, pX, x, y, B, LD)
-    want = expected_terms(fx, c).copy()
+    want = expected_terms(fx, k).copy()
     want[:, 2, 5] = np.nan
     want[:, 36, 69] = np.nan
     assert_bit_exact(terms[:, :, :B], want)
@@ -212,11 +169,10 @@ def test_launch_pair_is_capturable(gpu, fx):
     import torch
     from qamr.mutual_information import P_xhat, montecarlo_information_device
 
-    c = 5
-    pa, nm = make_nm(fx, c)
+    k = "c5_"
+    pa, nm = mapper(fx, k)
     pX = P_xhat(nm)
-    k = f"c{c}_"
-    x, y = to_dev(fx[k + "x"].astype(np.int64), LD, torch.int64), to_dev(fx[k + "y"], LD, torch.float64)
+    x, y = mc_inputs(fx, k, LD)
     eager = montecarlo_information_device(nm, pX, x, y, B).cpu().numpy()   # warm-up
     torch.cuda.synchronize()
     info = torch.zeros((3, LD), dtype=torch.float64, device="cuda")
@@ -232,7 +188,7 @@ def test_launch_pair_is_capturable(gpu, fx):
     torch.cuda.synchronize()
     assert_bit_exact(info.cpu().numpy()[:, :B], eager)
     assert_bit_exact(info.cpu().numpy()[:, :B], fx[k + "totals"].T)
-    assert_bit_exact(terms.cpu().numpy()[:, :, :B], expected_terms(fx, c))
+    assert_bit_exact(terms.cpu().numpy()[:, :, :B], expected_terms(fx, k))
 
 
 def test_device_entry_before_grid_or_tables_is_evalue(gpu):
@@ -316,11 +272,4 @@ def test_debug_build_mi_index_checks(gpu):
     """This file's parity tests in a child process on libqamr_debug.so: the symbol, decision and grid
     index checks of k_mi_terms (mi.hip QR_DCHECK) never fail -- conftest's autouse fixture fails any
     test after which one did."""
-    assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
-    env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
-                        *[f"tests/test_gpu_mi.py::{t}" for t in PARITY]], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-3000:]
-    assert r.returncode == 0, tail
-    assert f"{len(PARITY)} passed" in r.stdout, tail
+    rerun_on_debug_build([f"tests/test_gpu_mi.py::{t}" for t in PARITY], len(PARITY), timeout=600)

@@ -2,19 +2,18 @@
 tests/golden/make_golden_mi_quad.py: scipy.integrate.quad over the restated integrands of
 mutual_information.pyx:43-119 and :175-199, every NoiseMapper value from the compiled reference).  Every
 comparison is bit for bit (conftest.assert_bit_exact: infinities compare as bits, NaN matches NaN)."""
-import os
-import subprocess
-import sys
 import warnings
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bit_exact, golden
+from conftest import assert_bit_exact, golden
+
+from debug_rerun import rerun_on_debug_build
+from mapper_fixture import ORDER21, ORDER30, mapper, quad_expected
 
 pytestmark = pytest.mark.gpu
 
-DEBUG_LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr_debug.so")
 CASES = list(range(1, 11))
 
 
@@ -30,19 +29,7 @@ _NM = {}
 
 def make_nm(g, c):
     """One NoiseMapper per case for the whole module (its grid is built once)."""
-    import qamr
-
-    if c not in _NM:
-        k = f"c{c}_"
-        probs = g[k + "probs"]
-        pa = qamr.PAMAlphabet(int(g[k + "bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-        _NM[c] = qamr.NoiseMapper(pa, float(g[k + "noise_var"]), g[k + "cfg"])
-    return _NM[c]
-
-
-def expected(g, c, name):
-    k = f"c{c}_{name}_"
-    return float(g[k + "I"]), float(g[k + "abserr"]), int(g[k + "neval"]), bool(g[k + "warned"])
+    return mapper(g, f"c{c}_", cache=_NM)[1]
 
 
 def check_integrands(g, cases):
@@ -70,13 +57,6 @@ def test_integrands_vs_reference(gpu, fx, c):
     k = f"c{c}_"
     if c in (5, 8):   # an overflowed mixture (an infinite integrand value) is among these cases' stored points
         assert np.isinf(fx[k + "xy_f"]).sum() == 2
-
-
-# QUADPACK's evaluation sequence in the kernel's node numbering: dqk21 takes the centre, then the pairs
-# (below, above) of the even and of the odd nodes; dqk15i the centre's +T, -T, then per node f(T1), f(T2),
-# f(-T1), f(-T2)
-ORDER21 = [0] + [k for tw in (2, 4, 6, 8, 10) for k in (tw, 10 + tw)] + [k for tw in (1, 3, 5, 7, 9) for k in (tw, 10 + tw)]
-ORDER30 = [0, 1] + [s for j in range(1, 8) for s in (2 * j, 2 * (7 + j), 2 * j + 1, 2 * (7 + j) + 1)]
 
 
 def test_rule_nodes_are_the_abscissae_quad_visited(gpu, fx):
@@ -127,7 +107,7 @@ def test_integrals_vs_reference(gpu, fx, c):
     limit = int(fx[f"c{c}_limit"])
     for name, kind, pXs in (("base", "base", [P_xhat(nm)]), ("xy", "X_Y", None)):
         I, abserr, neval, ier = mutual_information_quad_batch(kind, [nm], pXs, limit=limit)
-        eI, eabs, eneval, ewarned = expected(fx, c, name)
+        eI, eabs, eneval, ewarned = quad_expected(fx, f"c{c}_", name)
         assert_bit_exact([I[0], abserr[0]], [eI, eabs])
         assert int(neval[0]) == eneval and (int(ier[0]) != 0) == ewarned, (name, neval, ier)
         st = quad_batch_stats()
@@ -153,7 +133,7 @@ def test_batch_equals_single_calls(gpu, fx, bps):
         nms = [make_nm(fx, c) for c in pick]
         for name, kind, pXs in (("base", "base", [P_xhat(nm) for nm in nms]), ("xy", "X_Y", None)):
             I, abserr, neval, ier = mutual_information_quad_batch(kind, nms, pXs)
-            exp = [expected(fx, c, name) for c in pick]
+            exp = [quad_expected(fx, f"c{c}_", name) for c in pick]
             assert_bit_exact(I, [e[0] for e in exp])
             assert_bit_exact(abserr, [e[1] for e in exp])
             assert neval.tolist() == [e[2] for e in exp]
@@ -263,11 +243,4 @@ def test_debug_build_quad_index_checks(gpu):
     """This file's parity tests in a child process on libqamr_debug.so: the node, LDS-slot, problem-id and grid
     index checks of k_mi_quad / k_mi_integrand (mi.hip, grid_interp.hpp QR_DCHECK) never fail -- conftest's autouse
     fixture fails any test after which one did."""
-    assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
-    env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
-                        *[f"tests/test_gpu_mi_quad.py::{t}" for t in PARITY]], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-3000:]
-    assert r.returncode == 0, tail
-    assert f"{len(PARITY)} passed" in r.stdout, tail
+    rerun_on_debug_build([f"tests/test_gpu_mi_quad.py::{t}" for t in PARITY], len(PARITY), timeout=600)

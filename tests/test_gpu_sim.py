@@ -8,20 +8,11 @@ import pytest
 from conftest import assert_bit_exact, assert_llr_close, golden
 
 import oracle as O
+from mapper_fixture import to_dev
 
 pytestmark = pytest.mark.gpu
 
 KEYS = [("b1_s20", 1), ("b2_s30", 2), ("b2_s95", 2), ("b4_s130", 4), ("b4_s250", 4)]
-
-
-def _col(arr, ld=64, dtype=None):
-    """One frame in column 0 of a frame-innermost [n, ld] device tensor."""
-    import torch
-
-    a = np.asarray(arr)
-    t = torch.zeros((a.size, ld), dtype=dtype or torch.float64, device="cuda")
-    t[:, 0] = torch.from_numpy(a.copy())
-    return t
 
 
 @pytest.mark.parametrize("key,bps", KEYS)
@@ -37,14 +28,14 @@ def test_direct_and_bare_llr_vs_reference(gpu, key, bps):
     y = g[f"{key}_y"]
     S = y.size
     out = torch.empty((S * bps, 64), dtype=torch.float64, device="cuda")
-    yt = _col(y)
+    yt = to_dev(y.reshape(S, 1), 64, torch.float64)   # one frame in column 0
     _lib.check(_lib.load().qr_direct_lappr_device(nm.handle, two_var, 1, 64, S, C.c_void_p(yt.data_ptr()),
                                                   C.c_void_p(out.data_ptr()), None))
     torch.cuda.synchronize()
     assert_bit_exact(out[:, 0].cpu().numpy(), g[f"{key}_direct"])
     # bare-LLR table lookup: bit-exact (host table is bit-exact, lookup is a copy)
     x = g[f"{key}_x"]
-    xt = _col(x, dtype=torch.int64)
+    xt = to_dev(x.reshape(S, 1), 64, torch.int64)
     table = torch.tensor(nm.bare_llr_table, dtype=torch.float64, device="cuda")
     _lib.check(_lib.load().qr_bare_llr_device(bps, C.c_void_p(table.data_ptr()), 1, 64, S, C.c_void_p(xt.data_ptr()),
                                               C.c_void_p(out.data_ptr()), None))

@@ -4,23 +4,18 @@ reference's own outputs (tests/golden/wide_interp_mi.npz, written by tests/golde
 shaped alphabets, sign configurations that set mask bits 32..63, grids of 41 201 to 519 862 points (coarse-table
 segments of 16, 32, 64 and 128 entries), and the under- and overflow of 64-PAM at 40 dB.  Every comparison is bit
 for bit (conftest.assert_bit_exact: infinities compare as bits, NaN matches NaN).  Only the fixture is read."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bit_exact, golden
+from conftest import assert_bit_exact, golden
+
+from debug_rerun import rerun_on_debug_build
 from decode_fixture import knobs
-from test_gpu_interp import block_expected, sha, to_dev
-from test_gpu_mi import run_device
-from test_gpu_mi import to_dev as mc_to_dev
-from test_gpu_mi_quad import ORDER21, ORDER30
+from mapper_fixture import (FIXTURE, ORDER21, ORDER30, block_expected, expected_terms, mapper, mc_inputs, quad_expected,
+                            run_device, sha, to_dev)
 
 pytestmark = pytest.mark.gpu
 
-DEBUG_LIB = os.path.join(ROOT, "qam-reconciliation_amd", "qamr", "libqamr_debug.so")
 CASES = list(range(1, 8))
 MC_CASES = [1, 2, 3, 4, 5, 7]
 QUAD_CASES = [1, 2, 3, 4, 5]
@@ -38,19 +33,10 @@ def fx():
 _NM = {}
 
 
-def make_nm(g, k, cfg=None):
+def make_nm(g, k, cfg=FIXTURE):
     """-> (PAMAlphabet, NoiseMapper), one per case for the whole module (its grid is built once); cfg replaces
     the case's sign configuration (a mapper of its own, cached likewise)."""
-    import qamr
-
-    at = (k, None if cfg is None else bytes(cfg))
-    if at not in _NM:
-        key = f"w{k}_"
-        probs = g[key + "probs"]
-        pa = qamr.PAMAlphabet(int(g[key + "bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-        _NM[at] = (pa, qamr.NoiseMapper(pa, float(g[key + "noise_var"]), g[key + "cfg"] if cfg is None else cfg,
-                                        float(g[key + "trunc"]), int(g[key + "nips"])))
-    return _NM[at]
+    return mapper(g, f"w{k}_", cfg, cache=_NM)
 
 
 # ----------------------------------------------------------------------- grid
@@ -135,30 +121,25 @@ def test_device_block_vs_reference(gpu, fx, k):
 
 
 # ---------------------------------------------------------------- Monte-Carlo
-def expected_terms(g, k, nblk=B):
-    return np.ascontiguousarray(g[f"w{k}_terms"][:, :nblk, :].transpose(0, 2, 1))   # [3][S][B]
-
-
 @pytest.mark.parametrize("k", MC_CASES)
 def test_montecarlo_blocks_vs_reference(gpu, fx, k):
     """montecarlo_information_device at B = 70, ld = 128, S = 11 (two tiles, the second with 6 valid lanes): the
     terms, and the totals the compiled montecarlo_information returned; padding columns are not written; the same
     at B = 1, ld = 64; and montecarlo_information under the stored seeds of blocks 0 and 69."""
-    import torch
     from qamr.mutual_information import P_xhat, montecarlo_information
 
     pa, nm = make_nm(fx, k)
     key = f"w{k}_"
     pX = P_xhat(nm)
     assert_bit_exact(pX, fx[key + "p_Xhat"])
-    x, y = mc_to_dev(fx[key + "x"].astype(np.int64), LD, torch.int64), mc_to_dev(fx[key + "y"], LD, torch.float64)
+    x, y = mc_inputs(fx, key, LD)
     info, terms = run_device(nm, pX, x, y, B, LD)
-    assert_bit_exact(terms[:, :, :B], expected_terms(fx, k))
+    assert_bit_exact(terms[:, :, :B], expected_terms(fx, key))
     assert_bit_exact(info[:, :B], fx[key + "totals"].T)
     assert np.isnan(terms[:, :, B:]).all() and np.isnan(info[:, B:]).all()
-    x1, y1 = mc_to_dev(fx[key + "x"][:1].astype(np.int64), 64, torch.int64), mc_to_dev(fx[key + "y"][:1], 64, torch.float64)
+    x1, y1 = mc_inputs(fx, key, 64, 1)
     info1, terms1 = run_device(nm, pX, x1, y1, 1, 64)
-    assert_bit_exact(terms1[:, :, :1], expected_terms(fx, k, 1))
+    assert_bit_exact(terms1[:, :, :1], expected_terms(fx, key, 1))
     assert_bit_exact(info1[:, 0], fx[key + "totals"][0])
     assert np.isnan(terms1[:, :, 1:]).all() and np.isnan(info1[:, 1:]).all()
     for f in (0, 69):
@@ -175,15 +156,14 @@ def test_montecarlo_64pam_reference_search_and_which_masks(gpu, fx):
     """Case 2 (64-PAM, a configuration with bits on both sides of index 32) with the reference's own index search
     (interp_fast = 0), and each single-bit `which` mask: a disabled quantity is exactly 0.0 / N and its term plane
     is not written, the enabled one is unchanged."""
-    import torch
     from qamr.mutual_information import P_xhat
 
     k = 2
     pa, nm = make_nm(fx, k)
     key = f"w{k}_"
     pX = P_xhat(nm)
-    x, y = mc_to_dev(fx[key + "x"].astype(np.int64), LD, torch.int64), mc_to_dev(fx[key + "y"], LD, torch.float64)
-    exp_t, exp_i = expected_terms(fx, k), fx[key + "totals"].T
+    x, y = mc_inputs(fx, key, LD)
+    exp_t, exp_i = expected_terms(fx, key), fx[key + "totals"].T
     with knobs(interp_fast=0):
         info, terms = run_device(nm, pX, x, y, B, LD)
         assert_bit_exact(terms[:, :, :B], exp_t)
@@ -203,11 +183,6 @@ def test_montecarlo_64pam_reference_search_and_which_masks(gpu, fx):
 
 
 # ----------------------------------------------------------------- quadrature
-def expected(g, k, name):
-    key = f"w{k}_{name}_"
-    return float(g[key + "I"]), float(g[key + "abserr"]), int(g[key + "neval"]), bool(g[key + "warned"])
-
-
 @pytest.mark.parametrize("k", QUAD_CASES)
 def test_integrands_and_rule_nodes_vs_reference(gpu, fx, k):
     """Both integrands at the first 42 abscissae quad visited (the compiled reference's values); one work item of
@@ -248,7 +223,7 @@ def test_integrals_vs_reference(gpu, fx, k):
     limit = int(fx[f"w{k}_limit"])
     for name, kind, pXs in (("base", "base", [P_xhat(nm)]), ("xy", "X_Y", None)):
         I, abserr, neval, ier = mutual_information_quad_batch(kind, [nm], pXs, limit=limit)
-        eI, eabs, eneval, ewarned = expected(fx, k, name)
+        eI, eabs, eneval, ewarned = quad_expected(fx, f"w{k}_", name)
         assert_bit_exact([I[0], abserr[0]], [eI, eabs])
         assert int(neval[0]) == eneval and (int(ier[0]) != 0) == ewarned, (name, neval, ier)
         st = quad_batch_stats()
@@ -267,7 +242,7 @@ def test_batch_of_one_bps_equals_the_single_integrals(gpu, fx, bps):
     nms = [make_nm(fx, k)[1] for k in pick]
     for name, kind, pXs in (("base", "base", [P_xhat(nm) for nm in nms]), ("xy", "X_Y", None)):
         I, abserr, neval, ier = mutual_information_quad_batch(kind, nms, pXs)
-        exp = [expected(fx, k, name) for k in pick]
+        exp = [quad_expected(fx, f"w{k}_", name) for k in pick]
         assert_bit_exact(I, [e[0] for e in exp])
         assert_bit_exact(abserr, [e[1] for e in exp])
         assert neval.tolist() == [e[2] for e in exp]
@@ -291,7 +266,7 @@ def test_sign_configs_override_at_64pam(gpu, fx):
     pX = P_xhat(alt)
     assert_bit_exact(pX, fx[f"w{k}_p_Xhat"])   # p_Xhat does not depend on the configuration
     I, abserr, neval, ier = mutual_information_quad_batch("base", [alt, alt], [pX, pX], np.stack([cfg, alt_cfg]))
-    eI, eabs, eneval, ewarned = expected(fx, k, "base")
+    eI, eabs, eneval, ewarned = quad_expected(fx, "w2_", "base")
     assert_bit_exact([I[0], abserr[0]], [eI, eabs])
     assert int(neval[0]) == eneval and (int(ier[0]) != 0) == ewarned
     assert I[1] != I[0]   # the configuration matters
@@ -311,7 +286,7 @@ def test_base_integral_64pam_with_reference_search(gpu, fx):
     pa, nm = make_nm(fx, 2)
     with knobs(interp_fast=0):
         I, abserr, neval, ier = mutual_information_quad_batch("base", [nm], [P_xhat(nm)])
-    eI, eabs, eneval, ewarned = expected(fx, 2, "base")
+    eI, eabs, eneval, ewarned = quad_expected(fx, "w2_", "base")
     assert_bit_exact([I[0], abserr[0]], [eI, eabs])
     assert int(neval[0]) == eneval and (int(ier[0]) != 0) == ewarned
 
@@ -332,11 +307,4 @@ def test_debug_build_wide_index_checks(gpu):
     """This file's parity tests for cases 2, 3, 4 and 7 in a child process on libqamr_debug.so: the grid, coarse
     table, symbol, decision, node, LDS-slot and problem-id index checks (grid_interp.hpp, mi.hip QR_DCHECK) never fail --
     conftest's autouse fixture fails any test after which one did."""
-    assert os.path.exists(DEBUG_LIB), "libqamr_debug.so missing: run __graft_entry__.build() (make -C csrc)"
-    env = dict(os.environ, QAMR_LIB=DEBUG_LIB, QAMR_DEBUG_ASSERTS="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
-                        *[f"tests/test_gpu_wide_interp_mi.py::{t}" for t in PARITY]], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-3000:]
-    assert r.returncode == 0, tail
-    assert f"{len(PARITY)} passed" in r.stdout, tail
+    rerun_on_debug_build([f"tests/test_gpu_wide_interp_mi.py::{t}" for t in PARITY], len(PARITY), timeout=600)

@@ -3,21 +3,15 @@ runs the very functions the kernels of demap_interp.hip and mi.hip and qr_demap_
 grid_geometry / grid_point, grid_binsearch, grid_interp_fast, grid_g_inv, grid_demap_symbol -- as host code
 against the reference's outputs in tests/golden/interp.npz, bit for bit, once plain and once under the
 address and undefined-behaviour sanitizers.  No GPU."""
-import hashlib
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_bit_exact, golden
+from conftest import assert_bit_exact, golden
 
-CSRC = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from mapper_fixture import alphabet, sha
+from native_check import build, run
+
 N_CASES = 11
-SANITIZE = ["-g", "-fno-omit-frame-pointer", "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-            "-Xarch_host", "-fno-sanitize-recover=all"]
 
 
 @pytest.fixture(scope="module")
@@ -29,36 +23,15 @@ def fx():
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def exe(request, tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc unavailable")
-    d = tmp_path_factory.mktemp("interp_check_" + request.param)
-    subprocess.run([sys.executable, os.path.join(CSRC, "gen_glibc_tables.py"), str(d / "glibc_tables.inc")], check=True)
-    out = str(d / "interp_check")
-    cc = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
-                         *(SANITIZE if request.param == "sanitized" else []), "-I" + CSRC, "-I" + os.path.join(ROOT, "include"),
-                         "-I" + str(d), "-o", out, os.path.join(ROOT, "tests", "native", "interp_check.cpp")],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    return out
-
-
-def run(exe, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=600, env=env)
-    print(" ".join(args), "\n", r.stdout, r.stderr[-2000:])
-    assert r.returncode == 0, r.stdout + r.stderr[-2000:]
-    assert "runtime error" not in r.stdout + r.stderr and "AddressSanitizer" not in r.stdout + r.stderr
-    return r.stdout
+    return build(tmp_path_factory.mktemp("interp_check_" + request.param), "interp_check.cpp",
+                 sanitize=request.param == "sanitized")
 
 
 def dump_case(fx, c, path):
     """The raw input of `interp_check case`: every n300 point x every hypothesis, every n2000 / j2000 symbol."""
-    from qamr.alphabet import PAMAlphabet
-
     k = f"c{c}_"
-    bps = int(fx[k + "bps"])
-    pa = PAMAlphabet(bps, 2.0, fx[k + "probs"])
-    M = pa.order
+    pa = alphabet(fx, k)
+    bps, M = pa.bit_per_symbol, pa.order
     assert fx[k + "ginv"].shape == (M, fx["n300"].size) and fx[k + "la"].size == fx["n2000"].size * bps
     parts = [[bps, float(fx[k + "noise_var"]), float(fx[k + "trunc"]), float(fx[k + "nips"]), 2.0],
              pa.constellation, pa.probabilities, pa.thresholds, fx[k + "cfg"],
@@ -66,10 +39,6 @@ def dump_case(fx, c, path):
              [fx["n2000"].size], fx["n2000"], fx[k + "j2000"], fx[k + "la"]]
     np.concatenate([np.asarray(p, np.float64).ravel() for p in parts]).tofile(path)
     return bps, M
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a, np.float64).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("c", range(N_CASES))

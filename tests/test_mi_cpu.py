@@ -3,17 +3,15 @@ the fixture (tests/golden/mi.npz, written by tests/golden/make_golden_mi.py), th
 evaluators, the restated glibc log2 and the per-sample arithmetic (tests/native/mi_check.cpp calls
 the very function the kernel calls), the entry points' argument checks and the CLI's defaults."""
 import os
-import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, assert_bit_exact, golden
 
-CSRC = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+import native_check
+from mapper_fixture import alphabet, host_mapper
+
 CASES = range(1, 9)
 B, S, N_YHAT = 70, 37, 5
 
@@ -21,23 +19,6 @@ B, S, N_YHAT = 70, 37, 5
 @pytest.fixture(scope="module")
 def fx():
     return golden("mi.npz")
-
-
-def alphabet(fx, c):
-    import qamr
-
-    probs = fx[f"c{c}_probs"]
-    return qamr.PAMAlphabet(int(fx[f"c{c}_bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-
-
-def host_nm(fx, c):
-    """What P_xhat / mutual_information_X_Xhat read of a NoiseMapper, from the pure host_tables."""
-    from qamr.noisemapper import host_tables
-
-    pa = alphabet(fx, c)
-    sigma = float(np.sqrt(float(fx[f"c{c}_noise_var"])))
-    fw = host_tables(pa.constellation, pa.thresholds, pa.probabilities, sigma, pa.bit_per_symbol)[0]
-    return pa, types.SimpleNamespace(order=pa.order, probabilities=pa.probabilities, fwrd_transition_probability=fw)
 
 
 def test_reference_import_line_resolves():
@@ -92,7 +73,7 @@ def test_fixture_draw_order_is_the_references(fx):
     """An array draw np.random.randn(S) after random_symbols equals the S scalar draws, and the
     fixture's blocks are those draws (PAMAlphabet.random_symbols uses numpy's global stream)."""
     for c in (2, 4, 6):
-        pa = alphabet(fx, c)
+        pa = alphabet(fx, f"c{c}_")
         sigma = float(np.sqrt(float(fx[f"c{c}_noise_var"])))
         for f in (0, 69):
             np.random.seed(5000 + 100 * c + f)
@@ -106,7 +87,7 @@ def test_fixture_draw_order_is_the_references(fx):
 def test_host_evaluators_bit_exact(fx, c):
     from qamr.mutual_information import P_xhat, mutual_information_X_Xhat
 
-    pa, nm = host_nm(fx, c)
+    pa, nm = host_mapper(fx, f"c{c}_")
     assert_bit_exact(nm.fwrd_transition_probability, fx[f"c{c}_fwrd"])
     pX = P_xhat(nm)
     assert_bit_exact(pX, fx[f"c{c}_p_Xhat"])
@@ -116,7 +97,7 @@ def test_host_evaluators_bit_exact(fx, c):
 def dump_case(fx, c, path):
     """The raw input of `mi_check sample`: header, tables, then per block x, x_hat, y, y_hat, terms, totals."""
     k = f"c{c}_"
-    pa = alphabet(fx, c)
+    pa = alphabet(fx, k)
     parts = [np.array([pa.bit_per_symbol, N_YHAT, S, float(fx[k + "noise_var"])]), pa.constellation, pa.probabilities,
              pa.thresholds, fx[k + "cfg"], fx[k + "p_Xhat"], fx[k + "fwrd"]]
     for f in range(N_YHAT):
@@ -125,47 +106,23 @@ def dump_case(fx, c, path):
     np.concatenate([np.asarray(p, np.float64).ravel() for p in parts]).tofile(path)
 
 
-def build_check(tmp_path, name, extra):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc unavailable")
-    inc = tmp_path / "glibc_tables.inc"
-    if not inc.exists():
-        subprocess.run([sys.executable, os.path.join(CSRC, "gen_glibc_tables.py"), str(inc)], check=True)
-    exe = str(tmp_path / name)
-    cc = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17", *extra, "-I" + CSRC,
-                         "-I" + os.path.join(ROOT, "include"), "-I" + str(tmp_path), "-o", exe,
-                         os.path.join(ROOT, "tests", "native", "mi_check.cpp")], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    return exe
-
-
 def run_check(exe, fx, tmp_path, n_log2):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, "log2", str(n_log2)], capture_output=True, text=True, timeout=600, env=env)
-    print(run.stdout, run.stderr[-2000:])
-    assert run.returncode == 0, run.stdout + run.stderr[-2000:]
+    native_check.run(exe, "log2", str(n_log2))
     for c in CASES:
         path = str(tmp_path / f"case{c}.bin")
         dump_case(fx, c, path)
-        run = subprocess.run([exe, "sample", path], capture_output=True, text=True, timeout=600, env=env)
-        print(f"case {c}:\n{run.stdout}", run.stderr[-2000:])
-        assert run.returncode == 0, f"case {c}: " + run.stdout + run.stderr[-2000:]
-        assert f"{N_YHAT * S * 3} inputs, 0 mismatches" in run.stdout
-        assert "runtime error" not in run.stdout + run.stderr and "AddressSanitizer" not in run.stdout + run.stderr
+        assert f"{N_YHAT * S * 3} inputs, 0 mismatches" in native_check.run(exe, "sample", path), c
 
 
 def test_log2_and_sample_arithmetic_bit_exact(fx, tmp_path):
     """g_log2_full == libm's log2 on 18 M inputs; mi_sample_terms on the fixture's x, x_hat, y, y_hat
     gives the fixture's terms and totals (and mi_bob its x_hat), every case."""
-    run_check(build_check(tmp_path, "mi_check", []), fx, tmp_path, 4000000)
+    run_check(native_check.build(tmp_path, "mi_check.cpp"), fx, tmp_path, 4000000)
 
 
 def test_log2_and_sample_arithmetic_under_sanitizers(fx, tmp_path):
     """The same stand-alone program with the address and undefined-behaviour sanitizers on the host code."""
-    exe = build_check(tmp_path, "mi_check_san",
-                      ["-g", "-fno-omit-frame-pointer", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
-                       "-fno-sanitize-recover=all"])
-    run_check(exe, fx, tmp_path, 300000)
+    run_check(native_check.build(tmp_path, "mi_check.cpp", exe_name="mi_check_san", sanitize=True), fx, tmp_path, 300000)
 
 
 def test_entry_points_refuse_bad_arguments_before_any_device_call():

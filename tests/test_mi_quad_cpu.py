@@ -6,7 +6,6 @@ configuration lists, and the reference's import lines."""
 import ctypes as C
 import math
 import os
-import subprocess
 import sys
 import types
 
@@ -15,8 +14,9 @@ import pytest
 
 from conftest import ROOT, assert_bit_exact, golden
 
-CSRC = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+import native_check
+from mapper_fixture import alphabet
+
 CASES = range(1, 11)
 HOST_INTEGRAL_CASES = (1, 2, 3, 4, 5, 9, 10)   # the 2-PAM and 4-PAM cases: both integrals wholly on the host
 
@@ -26,13 +26,6 @@ def fx():
     return golden("mi_quad.npz")
 
 
-def alphabet(fx, c):
-    import qamr
-
-    probs = fx[f"c{c}_probs"]
-    return qamr.PAMAlphabet(int(fx[f"c{c}_bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-
-
 def test_fixture_is_well_formed(fx):
     assert int(fx["n_cases"]) == 10
     assert [int(fx[f"c{c}_bps"]) for c in CASES] == [1, 1, 2, 2, 2, 3, 4, 4, 2, 2]
@@ -40,7 +33,7 @@ def test_fixture_is_well_formed(fx):
     for c in CASES:
         k = f"c{c}_"
         M = 1 << int(fx[k + "bps"])
-        pa = alphabet(fx, c)
+        pa = alphabet(fx, k)
         assert fx[k + "cfg"].shape == (M,) and fx[k + "p_Xhat"].shape == (M,) and abs(fx[k + "p_Xhat"].sum() - 1) < 1e-9
         assert fx[k + "base_x"].shape == fx[k + "base_f"].shape and fx[k + "xy_x"].shape == fx[k + "xy_f"].shape
         nb, nx = min(64, int(fx[k + "base_neval"])), min(64, int(fx[k + "xy_neval"]))
@@ -77,7 +70,7 @@ def dump_case(fx, c, path, integrals):
     from qamr.mutual_information import GRID_DEFAULTS
 
     k = f"c{c}_"
-    pa = alphabet(fx, c)
+    pa = alphabet(fx, k)
     parts = [np.array([pa.bit_per_symbol, float(fx[k + "noise_var"]), float(fx[k + "limit"]), GRID_DEFAULTS[0], GRID_DEFAULTS[1],
                        float(pa.step), float(integrals)]),
              pa.constellation, pa.probabilities, pa.thresholds, fx[k + "cfg"], fx[k + "p_Xhat"]]
@@ -88,37 +81,14 @@ def dump_case(fx, c, path, integrals):
     np.concatenate([np.asarray(p, np.float64).ravel() for p in parts]).tofile(path)
 
 
-def build_check(tmp_path, name, extra):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc unavailable")
-    inc = tmp_path / "glibc_tables.inc"
-    if not inc.exists():
-        subprocess.run([sys.executable, os.path.join(CSRC, "gen_glibc_tables.py"), str(inc)], check=True)
-    exe = str(tmp_path / name)
-    cc = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17", *extra, "-I" + CSRC,
-                         "-I" + os.path.join(ROOT, "include"), "-I" + str(tmp_path), "-o", exe,
-                         os.path.join(ROOT, "tests", "native", "mi_quad_check.cpp")], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    return exe
-
-
 def run_check(exe, fx, tmp_path):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-    def run(*args):
-        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=600, env=env)
-        print(" ".join(args), "\n", r.stdout, r.stderr[-2000:])
-        assert r.returncode == 0, r.stdout + r.stderr[-2000:]
-        assert "runtime error" not in r.stdout + r.stderr and "AddressSanitizer" not in r.stdout + r.stderr
-        return r.stdout
-
     path = str(tmp_path / "integrator.bin")
     dump_integrator(fx, path)
-    assert "24 records, 0 mismatches" in run("integrator", path)
+    assert "24 records, 0 mismatches" in native_check.run(exe, "integrator", path)
     for c in CASES:
         path = str(tmp_path / f"case{c}.bin")
         dump_case(fx, c, path, c in HOST_INTEGRAL_CASES)
-        out = run("case", path)
+        out = native_check.run(exe, "case", path)
         npts = fx[f"c{c}_base_x"].size + fx[f"c{c}_xy_x"].size
         assert f"{npts} points, 0 mismatches" in out
         assert ("2 on the host, 0 mismatches" in out) == (c in HOST_INTEGRAL_CASES)
@@ -128,15 +98,12 @@ def test_host_driver_and_integrands_bit_exact(fx, tmp_path):
     """The host integrator equals scipy's quad on the 24 integrator-only records; mi_base_arg / mi_xy_arg with
     host providers equal the fixture at every stored abscissa; both integrals of the 2-PAM and 4-PAM cases,
     wholly on the host through the same driver, equal the fixture's."""
-    run_check(build_check(tmp_path, "mi_quad_check", []), fx, tmp_path)
+    run_check(native_check.build(tmp_path, "mi_quad_check.cpp"), fx, tmp_path)
 
 
 def test_host_driver_and_integrands_under_sanitizers(fx, tmp_path):
     """The same stand-alone program with the address and undefined-behaviour sanitizers on the host code."""
-    exe = build_check(tmp_path, "mi_quad_check_san",
-                      ["-g", "-fno-omit-frame-pointer", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
-                       "-fno-sanitize-recover=all"])
-    run_check(exe, fx, tmp_path)
+    run_check(native_check.build(tmp_path, "mi_quad_check.cpp", exe_name="mi_quad_check_san", sanitize=True), fx, tmp_path)
 
 
 INTEGRANDS = (

@@ -3,15 +3,13 @@ for, the sizing rule) in a stand-alone program under sanitizers against numpy's 
 the keyword checks of the simulations, and the new entries of the C-ABI."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
 
-CSRC = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+import native_check
 
 ENTRIES = ("qr_npstream_create", "qr_npstream_destroy", "qr_npstream_state", "qr_npstream_words_device",
            "qr_npstream_random_sample_device", "qr_npstream_standard_normal_device", "qr_npstream_choice_device",
@@ -45,28 +43,14 @@ def test_host_pieces_under_asan_ubsan(tmp_path):
     np.random.get_state()'s key are np.random.bytes' words; the key and pos rebuilt from the tempered
     words at an offset are np.random.get_state() after that many words (offsets inside a block, on a
     block's end, several blocks on; a stream that starts at pos = 624, 1 and 623); the sizing rule."""
-    cxx = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(cxx):
-        pytest.skip("hipcc unavailable")
-    exe = str(tmp_path / "npstream_check")
-    san = []
-    for f in ("-fsanitize=address", "-fsanitize=undefined", "-fno-sanitize-recover=all"):
-        san += ["-Xarch_host", f]
-    cc = subprocess.run([cxx, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                         "-fno-omit-frame-pointer", *san, "-I" + CSRC, "-o", exe,
-                         os.path.join(ROOT, "tests", "native", "npstream_check.cpp")], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
+    exe = native_check.build(tmp_path, "npstream_check.cpp", opt="-O1", sanitize=True, extra=["-fno-fast-math"])
     for i, (seed, adv) in enumerate([(0, 0), (1, 1), (2 ** 32 - 1, 623), (7, 300)]):
         path = str(tmp_path / f"case{i}.bin")
         n = 3 * 624 + 1
         first_end = (624 - adv) % 624   # words to the end of the starting block (adv = 0: it stands there)
         offsets = sorted({0, 1, first_end, first_end + 1, first_end + 624, 1248, n})
         write_case(path, seed, adv, n, [c for c in offsets if 0 <= c <= n])
-        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=600, env=ENV)
-        out = r.stdout + r.stderr
-        assert r.returncode == 0, out[-3000:]
-        assert "runtime error" not in out and "AddressSanitizer" not in out
-        assert "npstream_check ok" in out
+        assert "npstream_check ok" in native_check.run(exe, path)
 
 
 def test_stream_keyword_errors(monkeypatch):

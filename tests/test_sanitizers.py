@@ -11,22 +11,12 @@ Both run with -fno-sanitize-recover=all: any report is a non-zero exit."""
 import os
 import shutil
 import subprocess
-import sys
 
 import pytest
 
 from conftest import ROOT
 
-CSRC = os.path.join(ROOT, "qam-reconciliation_amd", "csrc")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-
-def _run(exe):
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=ENV)
-    out = r.stdout + r.stderr
-    print(out[-3000:])
-    assert r.returncode == 0, out[-3000:]
-    assert "runtime error" not in out and "AddressSanitizer" not in out
+from native_check import build, run
 
 
 def test_oracle_under_asan_ubsan():
@@ -34,23 +24,8 @@ def test_oracle_under_asan_ubsan():
         pytest.skip("gcc unavailable")
     b = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "asan"], capture_output=True, text=True)
     assert b.returncode == 0, b.stderr[-2000:]
-    _run(os.path.join(ROOT, "oracle", "_asan", "oracle_asan"))
+    run(os.path.join(ROOT, "oracle", "_asan", "oracle_asan"))
 
 
 def test_libqamr_host_code_under_asan_ubsan(tmp_path):
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc unavailable")
-    subprocess.run([sys.executable, os.path.join(CSRC, "gen_glibc_tables.py"), str(tmp_path / "glibc_tables.inc")],
-                   check=True)
-    exe = str(tmp_path / "host_asan_check")
-    san = []
-    for f in ("-fsanitize=address", "-fsanitize=undefined", "-fno-sanitize-recover=all"):
-        san += ["-Xarch_host", f]
-    cc = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                         "-fno-fast-math", "-fno-omit-frame-pointer", *san, "-I" + CSRC, "-I" + str(tmp_path),
-                         "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                         os.path.join(ROOT, "tests", "native", "host_asan_check.cpp")],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-3000:]
-    _run(exe)
+    run(build(tmp_path, "host_asan_check.cpp", opt="-O1", sanitize=True, extra=["-fno-fast-math"]))

@@ -4,18 +4,16 @@ generator's conditions; the host-side tables (host_tables, P_xhat, mutual_inform
 montecarlo_information and -- through the native replays tests/native/mi_check.cpp and mi_quad_check.cpp, which
 call the very functions the kernels call -- the per-sample and per-abscissa arithmetic of mi_math.hpp and the
 host integrator equal the reference bit for bit before any GPU is involved."""
-import hashlib
 import os
 import re
-import subprocess
-import types
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, assert_bit_exact, golden
-from test_mi_cpu import build_check as build_mi_check
-from test_mi_quad_cpu import build_check as build_quad_check
+
+import native_check
+from mapper_fixture import alphabet, host_mapper, sha
 
 PATH = os.path.join(ROOT, "tests", "golden", "wide_interp_mi.npz")
 CASES = range(1, 8)
@@ -40,27 +38,6 @@ def fx():
     return golden("wide_interp_mi.npz")
 
 
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a, np.float64).tobytes()).hexdigest()
-
-
-def alphabet(fx, k):
-    import qamr
-
-    probs = fx[f"w{k}_probs"]
-    return qamr.PAMAlphabet(int(fx[f"w{k}_bps"]), 2.0, None if np.all(probs == probs[0]) else probs)
-
-
-def host_nm(fx, k):
-    """What P_xhat / mutual_information_X_Xhat read of a NoiseMapper, from the pure host_tables."""
-    from qamr.noisemapper import host_tables
-
-    pa = alphabet(fx, k)
-    sigma = float(np.sqrt(float(fx[f"w{k}_noise_var"])))
-    fw = host_tables(pa.constellation, pa.thresholds, pa.probabilities, sigma, pa.bit_per_symbol)[0]
-    return pa, types.SimpleNamespace(order=pa.order, probabilities=pa.probabilities, fwrd_transition_probability=fw)
-
-
 def test_fixture_is_well_formed(fx):
     assert int(fx["n_cases"]) == 7 and int(fx["B"]) == B and int(fx["S"]) == S
     assert os.path.getsize(PATH) <= 1_500_000
@@ -69,7 +46,7 @@ def test_fixture_is_well_formed(fx):
         bps, snr, shaped, cfgkind, grid, above = TABLE[k]
         key = f"w{k}_"
         M = 1 << bps
-        pa = alphabet(fx, k)
+        pa = alphabet(fx, key)
         assert int(fx[key + "bps"]) == bps and pa.order == M
         assert (float(fx[key + "trunc"]), int(fx[key + "nips"])) == grid
         probs, cfg = fx[key + "probs"], fx[key + "cfg"]
@@ -174,7 +151,7 @@ def test_host_tables_bit_exact(fx, k):
     from qamr.mutual_information import P_xhat, mutual_information_X_Xhat
 
     key = f"w{k}_"
-    pa, nm = host_nm(fx, k)
+    pa, nm = host_mapper(fx, key)
     fw = nm.fwrd_transition_probability
     assert_bit_exact(fw[0], fx[key + "fwrd_first"])
     assert_bit_exact(fw[-1], fx[key + "fwrd_last"])
@@ -189,7 +166,7 @@ def test_fixture_draw_order_is_the_references(fx):
     """PAMAlphabet.random_symbols and the S scalar normal draws under np.random.seed(9000 + 100 k + f) give the
     fixture's blocks, at the shaped 32-PAM and 8-PAM alphabets and at uniform 64-PAM."""
     for k in (2, 4, 5, 7):
-        pa = alphabet(fx, k)
+        pa = alphabet(fx, f"w{k}_")
         sigma = float(np.sqrt(float(fx[f"w{k}_noise_var"])))
         for f in (0, 69):
             np.random.seed(9000 + 100 * k + f)
@@ -203,7 +180,7 @@ def dump_mc_case(fx, k, path):
     """The raw input of `mi_check sample` (tests/test_mi_cpu.dump_case's layout) for a case of this fixture; the
     fwrd table is host_tables', whose digest test_host_tables_bit_exact pins."""
     key = f"w{k}_"
-    pa, nm = host_nm(fx, k)
+    pa, nm = host_mapper(fx, key)
     assert sha(nm.fwrd_transition_probability) == str(fx[key + "fwrd_sha"])
     parts = [np.array([pa.bit_per_symbol, N_YHAT, S, float(fx[key + "noise_var"])]), pa.constellation, pa.probabilities,
              pa.thresholds, fx[key + "cfg"], fx[key + "p_Xhat"], nm.fwrd_transition_probability]
@@ -216,7 +193,7 @@ def dump_mc_case(fx, k, path):
 def dump_quad_case(fx, k, path, integrals):
     """The raw input of `mi_quad_check case` (tests/test_mi_quad_cpu.dump_case's layout)."""
     key = f"w{k}_"
-    pa = alphabet(fx, k)
+    pa = alphabet(fx, key)
     parts = [np.array([pa.bit_per_symbol, float(fx[key + "noise_var"]), float(fx[key + "limit"]), float(fx[key + "trunc"]),
                        float(fx[key + "nips"]), float(pa.step), float(integrals)]),
              pa.constellation, pa.probabilities, pa.thresholds, fx[key + "cfg"], fx[key + "p_Xhat"]]
@@ -227,29 +204,16 @@ def dump_quad_case(fx, k, path, integrals):
     np.concatenate([np.asarray(p, np.float64).ravel() for p in parts]).tofile(path)
 
 
-SANITIZE = ["-g", "-fno-omit-frame-pointer", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
-            "-fno-sanitize-recover=all"]
-
-
-def run_native(exe, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=600, env=env)
-    print(" ".join(args), "\n", r.stdout, r.stderr[-2000:])
-    assert r.returncode == 0, r.stdout + r.stderr[-2000:]
-    assert "runtime error" not in r.stdout + r.stderr and "AddressSanitizer" not in r.stdout + r.stderr
-    return r.stdout
-
-
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitizers"])
 def test_sample_arithmetic_bit_exact(fx, tmp_path, sanitize):
     """mi_sample_terms (mi_math.hpp, the function k_mi_terms calls) on the fixture's x, x_hat, y and y_hat of the
     first 5 blocks gives the fixture's terms and the compiled reference's totals, and mi_bob its x_hat, at
     8-, 32- and 64-PAM; once more with the address and undefined-behaviour sanitizers on the host code."""
-    exe = build_mi_check(tmp_path, "mi_check_wide" + ("_san" if sanitize else ""), SANITIZE if sanitize else [])
+    exe = native_check.build(tmp_path, "mi_check.cpp", exe_name="mi_check_wide" + ("_san" if sanitize else ""), sanitize=sanitize)
     for k in MC_CASES:
         path = str(tmp_path / f"mc{k}.bin")
         dump_mc_case(fx, k, path)
-        out = run_native(exe, "sample", path)
+        out = native_check.run(exe, "sample", path)
         assert f"{N_YHAT * S * 3} inputs, 0 mismatches" in out and f"{N_YHAT * S} samples, 0 mismatches" in out, (k, out)
 
 
@@ -258,12 +222,13 @@ def test_integrands_and_host_integrals_bit_exact(fx, tmp_path, sanitize):
     """mi_base_arg / mi_xy_arg (the functions k_mi_quad calls) with host providers -- g_inv on a host-built grid of
     up to 144 244 points -- equal the compiled reference's integrands at every stored abscissa of cases 1..5; in
     the plain build both integrals run wholly on the host through the batch's driver and equal the fixture's."""
-    exe = build_quad_check(tmp_path, "mi_quad_check_wide" + ("_san" if sanitize else ""), SANITIZE if sanitize else [])
+    exe = native_check.build(tmp_path, "mi_quad_check.cpp", exe_name="mi_quad_check_wide" + ("_san" if sanitize else ""),
+                             sanitize=sanitize)
     for k in QUAD_CASES:
         path = str(tmp_path / f"quad{k}.bin")
         integrals = not sanitize or k == 5
         dump_quad_case(fx, k, path, integrals)
-        out = run_native(exe, "case", path)
+        out = native_check.run(exe, "case", path)
         npts = fx[f"w{k}_base_x"].size + fx[f"w{k}_xy_x"].size
         assert f"{npts} points, 0 mismatches" in out, (k, out)
         assert ("2 on the host, 0 mismatches" in out) == integrals, (k, out)
