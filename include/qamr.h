@@ -299,6 +299,55 @@ QR_API int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x
  * arrays of n elements, synchronous.  For tests.  Not a reference interface. */
 QR_API int qr_log2_host(int64_t n, const double *x, double *out);
 
+/* The arithmetic primitives of the bit-exact paths (glibc exp / log, the box-plus built from them,
+ * cephes erf, the demapper's division by 2 sigma^2), evaluated on the device element by element:
+ * out[k] = fn(a[k]) or fn(a[k], b[k]), host arrays of n elements, synchronous, on the caller's current
+ * device.  For tests (tests/test_gpu_device_math.py).  Not a reference interface.
+ *
+ * Each fn is one kernel that calls the device function as the product kernels call it; `variant` names
+ * the table home (and GlibcK form) of a product call site:
+ *   QR_MATH_HOME_SWEEP   GlibcTablesBP in LDS, staged from a code handle's table (built on the host by
+ *                        build_glibc_tables), GlibcK::pinned(): the check sweeps (decoder.hip
+ *                        check_block / check_exact, the runtime-degree sweep), the frame-resident decode
+ *                        (decode_small.hip) and the few-frame decode (decode_few.hip)
+ *   QR_MATH_HOME_NODE    GlibcTables in LDS from the same table, default GlibcK: k_check_nodes
+ *                        (decode_api.hip, qr_process_check_nodes_host)
+ *   QR_MATH_HOME_CONST   the __constant__ kGlibcConst read in place: k_direct_lappr (demap.hip), erfc_ge1
+ *                        (qamr_math.hpp), the per-symbol formulation-1 demapper (demap_interp.hip), the
+ *                        polar Box-Muller of npstream.hip
+ *   QR_MATH_HOME_EXPLOG  GlibcExpLog in LDS, staged from kGlibcConst: k_demap_wave (demap.hip) and the
+ *                        wave formulation-1 demapper (demap_interp.hip)
+ *   QR_MATH_HOME_DEMAP   GlibcTables in LDS, staged from kGlibcConst: k_demap / demap_symbol
+ *   QR_MATH_HOME_MI      {exp table, log2 table} in LDS, copied from kGlibcConst: k_mi_terms, k_mi_quad
+ * and the homes each fn accepts (any other is QR_EVALUE):
+ *   EXP (g_exp, |a| < 512 or NaN; no product call site of its own)        NODE, CONST
+ *   EXP_NEG (g_exp_neg, a in [-37.51, 0] or NaN), LOG_U, LOG_U_SEL (a in [1, 2] or NaN),
+ *   H_STRICT, H_STRICT_SEL (h_strict<false / true>, any a),
+ *   BOX_PLUS, BOX_PLUS_SEL (box_plus_strict_t<false / true>(a, b))       SWEEP, NODE
+ *   EXP_FULL, LOG_FULL (any a), LOG (g_log, a positive normal; reached through g_log_full)
+ *                                                                         CONST, EXPLOG, DEMAP
+ *   EXP_WAVE (g_exp_wave, any a; wavefront w holds elements [64 w, 64 w + 64))   EXPLOG, MI
+ *   ERF (cephes_erf, any a; its erfc branch reads kGlibcConst)            CONST
+ *   DIV_TWO_S2 (a / b by div_two_s2 with two_s2 = b[k], inv_two_s2 = RN(1 / b[k]) formed on the host as
+ *     the demapper's tables form it)                                      CONST
+ *   H_PACKED (strict_pack.hpp h_packed<clamp>, nj arguments per lane, home SWEEP -- its only call sites):
+ *     variant = clamp * 8 + (nj - 1), clamp 0 = kClampNone, 1 = kClampFull, 2 = kClampFinite, nj 1..8;
+ *     wavefront w holds elements [64 nj w, 64 nj (w + 1)), argument j of lane l at 64 nj w + 64 j + l;
+ *     out[k] = h(|a[k]|) = log(1.0 + exp(-|a[k]|)).
+ * Lanes past n run along on the argument 1.0 and store nothing.  b is read by BOX_PLUS, BOX_PLUS_SEL
+ * and DIV_TWO_S2 only (NULL otherwise).  QR_EVALUE: an unknown fn or variant, n < 0, a null array with
+ * n > 0; n == 0 is QR_OK before any device call. */
+enum {
+    QR_MATH_EXP = 0, QR_MATH_EXP_NEG, QR_MATH_EXP_FULL, QR_MATH_EXP_WAVE, QR_MATH_LOG, QR_MATH_LOG_U, QR_MATH_LOG_U_SEL,
+    QR_MATH_LOG_FULL, QR_MATH_H_STRICT, QR_MATH_H_STRICT_SEL, QR_MATH_BOX_PLUS, QR_MATH_BOX_PLUS_SEL, QR_MATH_ERF,
+    QR_MATH_DIV_TWO_S2, QR_MATH_H_PACKED
+};
+enum {
+    QR_MATH_HOME_SWEEP = 0, QR_MATH_HOME_NODE, QR_MATH_HOME_CONST, QR_MATH_HOME_EXPLOG, QR_MATH_HOME_DEMAP,
+    QR_MATH_HOME_MI
+};
+QR_API int qr_math_eval_host(int32_t fn, int32_t variant, int64_t n, const double *a, const double *b, double *out);
+
 /* ------------------------------ quad-integrated mutual information */
 /* mutual_information_base_scheme (mutual_information.pyx:123-148, kind 0: the integral of
  * mutual_information_base_scheme_arg, :43-119, over [0, 1]) and mutual_information_X_Y (:202-208, kind 1:

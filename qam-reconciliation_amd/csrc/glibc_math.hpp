@@ -28,8 +28,14 @@
 //       log = fma(r^3, fma(fma(r, A4, A3), r^2, fma(r, A2, A1)), fma(r^2, A0, lo)) + hi.
 //
 // tests/test_glibc_math.py runs these on the host against libm's exp/log on ~10^7
-// inputs (dense on the box-plus domain) and requires identical bits; the GPU tests
-// then require decodes bit-identical to the oracle (which calls libm).
+// inputs (dense on the box-plus domain) and requires identical bits.  The gfx950 compile
+// (inline assembly, the device-only g_exp_wave and h_packed, each kernel's table home and
+// GlibcK form) is compared with libm too: qr_math_eval_host (math_eval.hip) runs every
+// function below on the device as the product kernels call it, and
+// tests/test_gpu_device_math.py requires identical bits on ~2 10^5 inputs per function,
+// the over- and underflowing, subnormal and non-finite ones included (g_log2_full:
+// qr_log2_host, tests/test_gpu_mi.py).  The other GPU tests then require decodes and
+// demapped LAPPRs bit-identical to the oracle (which calls libm).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

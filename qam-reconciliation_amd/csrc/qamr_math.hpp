@@ -649,15 +649,18 @@ inline void build_quantiles(const DemapTables &t, double2 *quant) {
 // No overflow or underflow occurs for these arguments (|x| <= ~1e4, b = 2 sigma^2 > 0 normal),
 // except that x = -0 gives +0 (harmless: the quotient only feeds exp, exp(+-0) = 1).  Pinned on
 // the host against the IEEE division (tests/native/division_check.cpp: random, near-2 quotient
-// significands, the configured 2 sigma^2 of 2..16-PAM at 0..40 dB) and on the GPU by the
-// bit-exact demap tests.  The device's IEEE division is a ~10-instruction sequence
+// significands, the configured 2 sigma^2 of 2..16-PAM at 0..40 dB) and on the GPU on the same
+// input sets (qr_math_eval_host, tests/test_gpu_device_math.py) and by the bit-exact demap tests.  The device's IEEE division is a ~10-instruction sequence
 // (v_div_scale x2, v_rcp, fmas, v_div_fmas, v_div_fixup).
-QR_HD double div_two_s2(const DemapTables &t, double x) {
-    const double q0 = x * t.inv_two_s2;
-    const double q1 = __builtin_fma(__builtin_fma(-q0, t.two_s2, x), t.inv_two_s2, q0);
-    const double r1 = __builtin_fma(-q1, t.two_s2, x);
-    return __builtin_fma(r1, t.inv_two_s2, q1);
+// The four operations on the two table values they read (the device test entry of math_eval.hip calls
+// the core with a 2 sigma^2 per element).
+QR_HD double div_two_s2_core(double two_s2, double inv_two_s2, double x) {
+    const double q0 = x * inv_two_s2;
+    const double q1 = __builtin_fma(__builtin_fma(-q0, two_s2, x), inv_two_s2, q0);
+    const double r1 = __builtin_fma(-q1, two_s2, x);
+    return __builtin_fma(r1, inv_two_s2, q1);
 }
+QR_HD double div_two_s2(const DemapTables &t, double x) { return div_two_s2_core(t.two_s2, t.inv_two_s2, x); }
 
 // noisemapper.pyx:450-540 for one symbol; out[k] = LAPPR of Gray bit k (LSB first).
 // Note the reference quirk kept on purpose: no /2sigma^2 for k < j (:503-507).

@@ -132,7 +132,7 @@ def test_entry_points_refuse_bad_arguments_before_any_device_call():
 
     L = _lib.load()
     for s in ("qr_demap_mi_tables", "qr_mi_workspace_size", "qr_mi_montecarlo_device", "qr_mi_montecarlo_host",
-              "qr_log2_host"):
+              "qr_log2_host", "qr_math_eval_host"):
         assert s in _lib.SIGNATURES and hasattr(L, s), s
     E = _lib.QR_EVALUE
     z = np.zeros(4)
@@ -154,6 +154,12 @@ def test_entry_points_refuse_bad_arguments_before_any_device_call():
     assert L.qr_log2_host(-1, None, None) == E
     assert L.qr_log2_host(3, None, None) == E
     assert L.qr_log2_host(0, None, None) == 0
+    # the other test-only device entry, same rule (every function and table home: tests/test_device_math_cpu.py)
+    assert L.qr_math_eval_host(2, 2, -1, None, None, None) == E
+    assert L.qr_math_eval_host(2, 2, 3, None, None, None) == E
+    assert "null" in _lib.last_error()
+    assert L.qr_math_eval_host(2, 2, 3, _lib.ptr(z), None, None) == E
+    assert L.qr_math_eval_host(2, 2, 0, None, None, None) == 0
 
 
 def test_cli_parser_defaults_match_the_reference():
