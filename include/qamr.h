@@ -299,6 +299,40 @@ QR_API int qr_mi_montecarlo_host(const qr_demap *dm, int64_t N, const int64_t *x
  * arrays of n elements, synchronous.  For tests.  Not a reference interface. */
 QR_API int qr_log2_host(int64_t n, const double *x, double *out);
 
+/* ------------------------------ LAPPR information rate (BICM generalised mutual information) */
+/* What the LAPPRs carry to the bit-wise decoder, at A scales alpha of the LAPPRs at once.  Not a
+ * reference interface; the definition is this library's and the results are bit-exact against it.
+ * Per element v = s * bit_per_symbol + k (symbol s, level k), word bit w in {0, 1} and scale alpha:
+ *   x = alpha * L, negated when w == 0;  m = x > 0 ? x : 0.0;
+ *   t = m * 1.4426950408889634 + log2(1.0 + exp(-|x|)),
+ * every operation rounded separately (no FMA), exp and log2 glibc's.  NaN gives NaN, x = +inf gives
+ * +inf, x = -inf gives 0.0.  The sums: a chunk is QR_LAPPR_INFO_CHUNK consecutive symbols of one frame
+ * and level, added from 0.0 in ascending s; loss[a][k][f] adds the frame's chunks from 0.0 in
+ * ascending order; total[a][k] adds loss[a][k][f] from 0.0 over f = 0 .. B-1.  errors[k][f] counts the
+ * elements whose decided bit (0 iff L >= 0, so NaN decides 1: utils.pyx:35-38, on the unscaled L)
+ * differs from w; total_errors[k] is their sum over the frames.  The rate of level k at scale a is
+ * 1 - total[a][k] / (B S) bits, the caller's division. */
+#define QR_LAPPR_INFO_CHUNK 256
+/* Bytes of the chunk sums qr_lappr_info_device needs as workspace.  QR_EVALUE unless bit_per_symbol
+ * in 1..8, ld > 0, ld % 64 == 0, S >= 1, A in 1..16. */
+QR_API int qr_lappr_info_workspace_size(int32_t bit_per_symbol, int32_t ld, int64_t S, int32_t A, size_t *bytes);
+/* The batch, frame-innermost as the decoder takes it: d_lappr [S*bps][ld] fp64, d_word [S*bps][ld]
+ * uint8, B frames in columns [0, B); alphas[A] in HOST memory (they travel as kernel arguments);
+ * d_loss [A][bps][ld] fp64, d_errors [bps][ld] int32, d_total [A][bps] fp64, d_total_errors [bps]
+ * int64.  The padding columns [B, ld) are neither read into any output nor written.
+ * QR_EVALUE: bit_per_symbol outside 1..8, A outside 1..16, a scale that is not finite, S < 1, B < 1,
+ * B > ld, ld % 64 != 0, a null pointer, a short workspace.  Two launches on `stream` of the current
+ * device, asynchronous, no allocation, capturable into a graph. */
+QR_API int qr_lappr_info_device(int32_t bit_per_symbol, int32_t B, int32_t ld, int64_t S, const double *d_lappr,
+                                const uint8_t *d_word, int32_t A, const double *alphas, double *d_loss,
+                                int32_t *d_errors, double *d_total, int64_t *d_total_errors, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+/* One frame from host memory in the reference's interleaved layout (lappr[S*bps], word[S*bps], element
+ * s * bps + k), through the same kernels on GPU `device`: loss[A][bps] fp64, errors[bps] int64.
+ * Synchronous. */
+QR_API int qr_lappr_info_host(int32_t device, int32_t bit_per_symbol, int64_t S, const double *lappr,
+                              const uint8_t *word, int32_t A, const double *alphas, double *loss, int64_t *errors);
+
 /* The arithmetic primitives of the bit-exact paths (glibc exp / log, the box-plus built from them,
  * cephes erf, the demapper's division by 2 sigma^2), evaluated on the device element by element:
  * out[k] = fn(a[k]) or fn(a[k], b[k]), host arrays of n elements, synchronous, on the caller's current

@@ -67,6 +67,9 @@ SIGNATURES = {
     "qr_mi_montecarlo_device": [vp, C.c_uint32, i32, i32, i64, vp, vp, vp, vp, vp, C.c_size_t, vp],
     "qr_mi_montecarlo_host": [vp, i64, vp, vp, vp, vp, vp],
     "qr_log2_host": [i64, vp, vp],
+    "qr_lappr_info_workspace_size": [i32, i32, i64, i32, P(C.c_size_t)],
+    "qr_lappr_info_device": [i32, i32, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp],
+    "qr_lappr_info_host": [i32, i32, i64, vp, vp, i32, vp, vp, vp],
     "qr_math_eval_host": [i32, i32, i64, vp, vp, vp],
     "qr_mi_quad_batch": [vp, vp, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp],
     "qr_mi_quad_stats": [vp],

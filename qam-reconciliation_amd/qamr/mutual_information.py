@@ -18,6 +18,10 @@ evaluates B such blocks, already in HBM, in one launch pair (qr_mi_montecarlo_de
 (qr_mi_quad_batch): the floats returned are the reference's, the integrals it returns as ``-inf``
 included.  ``mutual_information_quad_batch`` integrates many mappers / sign configurations in one call,
 one launch per round of bisections; the ``_arg_array`` forms evaluate an integrand over an array.
+
+``lappr_information`` and ``lappr_information_device`` are not the reference's: they estimate the rate the
+per-bit LAPPRs carry to the bit-wise decoder (the BICM generalised mutual information), at several scales
+alpha of the LAPPRs in one pass (qr_lappr_info_host / qr_lappr_info_device; DESIGN.md "LAPPR information rate").
 """
 from __future__ import annotations
 
@@ -32,7 +36,8 @@ from ._lib import bool_as_u8, check, check_2d, check_tensor, dptr, ptr, stream_a
 __all__ = ["P_xhat", "mutual_information_X_Xhat", "montecarlo_information", "montecarlo_information_device",
            "which_mask", "mutual_information_base_scheme_arg", "mutual_information_base_scheme_arg_array",
            "mutual_information_X_Y_int_arg", "mutual_information_X_Y_int_arg_array", "mutual_information_base_scheme",
-           "mutual_information_X_Y", "mutual_information_quad_batch", "quad_batch_stats", "quad_host", "quad_rule"]
+           "mutual_information_X_Y", "mutual_information_quad_batch", "quad_batch_stats", "quad_host", "quad_rule",
+           "lappr_information", "lappr_information_device", "LapprInformation"]
 
 GRID_DEFAULTS = (1e-21, 1000)   # NoiseMapper's trunkation_threshold, n_intervals_per_step (noisemapper.pyx:103-105)
 QUAD_KINDS = {"base": 0, "X_Y": 1}
@@ -157,6 +162,116 @@ def montecarlo_information_device(nm, p_Xhat, x_fi, y_fi, B, which=np.ones(3, dt
     if stream != current:   # the buffer came from the current stream's pool: keep it until `stream` is done with it
         t.record_stream(stream)
     return (info[:, :B], t) if want_terms else info[:, :B]
+
+
+# ------------------------------------------------------------------ LAPPR information rate
+LAPPR_INFO_CHUNK = 256        # QR_LAPPR_INFO_CHUNK (include/qamr.h): the symbols of one chunk sum
+LAPPR_INFO_MAX_SCALES = 16
+LAPPR_INFO_MAX_BPS = 8
+
+
+def _check_info_args(bps, alphas):
+    """bit_per_symbol in 1..8 and 1..16 finite scales, as the C-ABI requires them: (bps, float64 [A])."""
+    if isinstance(bps, bool) or int(bps) != bps or not 1 <= int(bps) <= LAPPR_INFO_MAX_BPS:
+        raise ValueError(f"bps must be an integer in 1..{LAPPR_INFO_MAX_BPS}, got {bps!r}")
+    al = np.ascontiguousarray(np.asarray(alphas, np.float64).ravel())
+    if not 1 <= al.size <= LAPPR_INFO_MAX_SCALES:
+        raise ValueError(f"alphas must hold 1..{LAPPR_INFO_MAX_SCALES} scales, got {al.size}")
+    if not np.all(np.isfinite(al)):
+        raise ValueError("alphas must be finite")
+    return int(bps), al
+
+
+def _info_rates(total, B, S):
+    """I_k(alpha) = 1.0 - total[a][k] / (B S) and I(alpha), their sum from 0.0 over ascending k (float64)."""
+    total = np.asarray(total, np.float64)
+    A, bps = total.shape
+    n = float(int(B) * int(S))
+    I_level = np.empty((A, bps), np.float64)
+    I = np.empty(A, np.float64)
+    for a in range(A):
+        acc = 0.0
+        for k in range(bps):
+            v = 1.0 - float(total[a, k]) / n
+            I_level[a, k] = v
+            acc += v
+        I[a] = acc
+    return I, I_level
+
+
+def lappr_information(lappr, word, bps, alphas=(1.0,), device=0):
+    """The information rate one frame's LAPPRs carry to the bit-wise decoder (the BICM generalised mutual
+    information, bits per symbol) at every scale of `alphas`: lappr float64 [S * bps] and word uint8
+    [S * bps] (the bits the decoder must recover), element s * bps + k as the demappers return them ->
+    (I float64 [A], I_level float64 [A, bps], errors int64 [bps]); errors[k] counts level k's hard-decision
+    errors (count_errors_from_lappr's rule).  One synchronous host round trip (qr_lappr_info_host)."""
+    bps, al = _check_info_args(bps, alphas)
+    L = _lib.as_buffer(lappr, np.float64, name="lappr")
+    w = _lib.as_buffer(word, np.uint8, name="word")
+    if L.size != w.size:
+        raise ValueError(f"lappr has {L.size} elements, word {w.size}")
+    if L.size < bps or L.size % bps:
+        raise ValueError(f"lappr has {L.size} elements: not a positive multiple of bps = {bps}")
+    S = L.size // bps
+    loss = np.empty((al.size, bps), np.float64)
+    errors = np.empty(bps, np.int64)
+    check(_lib.load().qr_lappr_info_host(int(device), bps, S, ptr(L), ptr(w), al.size, ptr(al), ptr(loss), ptr(errors)),
+          "lappr_information")
+    I, I_level = _info_rates(loss, 1, S)
+    return I, I_level, errors
+
+
+class LapprInformation:
+    """What lappr_information_device wrote, on the device: loss float64 [A, bps, B] and errors int32
+    [bps, B] (views of the frames [0, B) of their [.., ld] buffers), total float64 [A, bps] and
+    total_errors int64 [bps]."""
+
+    def __init__(self, loss, errors, total, total_errors, B):
+        self.loss, self.errors, self.total, self.total_errors, self.B = loss, errors, total, total_errors, int(B)
+
+    def rates(self, S):
+        """-> host (I float64 [A], I_level float64 [A, bps], ber_level float64 [bps]) of a batch of S symbols
+        per frame; synchronises with the launches."""
+        total = self.total.cpu().numpy()
+        terr = self.total_errors.cpu().numpy()
+        I, I_level = _info_rates(total, self.B, S)
+        ber = np.array([float(e) / float(self.B * int(S)) for e in terr], np.float64)
+        return I, I_level, ber
+
+
+def lappr_information_device(lappr_fi, word_fi, B, bps, alphas=(1.0,), stream=None):
+    """B frames already in HBM, frame-innermost as the decoder takes them: lappr_fi float64 [S * bps, ld],
+    word_fi uint8 [S * bps, ld], frame f in column f -> LapprInformation.  Two launches on `stream`
+    (torch's current stream when None), asynchronous, every scale in one pass over the LAPPRs."""
+    import torch
+
+    bps, al = _check_info_args(bps, alphas)
+    V, ld = check_2d(lappr_fi, "lappr_information_device", "lappr_fi", "[S * bps, ld]")
+    if ld % 64 or not 0 < int(B) <= ld or V < bps or V % bps:
+        raise ValueError(f"lappr_information_device: need ld % 64 == 0, 0 < B <= ld and a positive multiple of bps = {bps} "
+                         f"rows (B={B}, ld={ld}, rows={V})")
+    check_tensor(lappr_fi, "lappr_fi", (V, ld), torch.float64)
+    dev = lappr_fi.device
+    check_tensor(word_fi, "word_fi", (V, ld), torch.uint8, dev.index)
+    S, A = V // bps, al.size
+    L = _lib.load()
+    need = C.c_size_t(0)
+    check(L.qr_lappr_info_workspace_size(bps, int(ld), S, A, C.byref(need)), "lappr_info_workspace_size")
+    current = torch.cuda.current_stream(dev)
+    stream, sp = stream_arg(stream, dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+        loss = torch.empty((A, bps, ld), dtype=torch.float64, device=dev)
+        errors = torch.empty((bps, ld), dtype=torch.int32, device=dev)
+        total = torch.empty((A, bps), dtype=torch.float64, device=dev)
+        total_errors = torch.empty((bps,), dtype=torch.int64, device=dev)
+        check(L.qr_lappr_info_device(bps, int(B), int(ld), S, dptr(lappr_fi), dptr(word_fi), A, ptr(al), dptr(loss),
+                                     dptr(errors), dptr(total), dptr(total_errors), dptr(ws), need.value, sp),
+              "lappr_information_device")
+    if stream != current:   # the buffers came from the current stream's pool: keep them until `stream` is done with them
+        for t in (ws, loss, errors, total, total_errors):
+            t.record_stream(stream)
+    return LapprInformation(loss[:, :, :B], errors[:, :B], total, total_errors, B)
 
 
 # ------------------------------------------------------------------ quad-integrated evaluators

@@ -50,6 +50,58 @@ def check_stream(stream: str) -> str:
     return stream
 
 
+def source_tables(pa: PAMAlphabet, device):
+    """What llr_source reads of the alphabet, on the device: (constellation, probabilities, uniform?)."""
+    import torch
+
+    return (torch.tensor(pa.constellation, dtype=torch.float64, device=device),
+            torch.tensor(pa.probabilities, dtype=torch.float64, device=device),
+            bool(np.all(pa.probabilities == pa.probabilities[0])))
+
+
+def llr_source(nm: NoiseMapper, pa: PAMAlphabet, S: int, B: int, gen, mode: str = "softening",
+               demapper: str = "search", alpha: float = 1.0, two_variance: float | None = None,
+               stream: str = "torch", tables=None):
+    """One batch of B frames of S symbols for `mode`, with no code involved: (lappr [S * bps, ld],
+    word [S * bps, ld]), the LAPPRs the decoder would be given and the word it must recover.
+    gen: a torch generator, or the NumpyStream the frames are drawn from (stream="numpy").
+    two_variance: the direct mode's 2 sigma^2 (reconciliation.pyx:191-192).  tables: source_tables(pa,
+    device), for a caller that keeps them."""
+    import torch
+
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}")
+    device = torch.device("cuda", nm._device)
+    a, p, uniform = source_tables(pa, device) if tables is None else tables
+    bps = pa.bit_per_symbol
+    ld = leading_dim(B)
+    sp = stream_arg(None, device)[1]
+    if stream == "numpy":                              # reconciliation.pyx:129-132, frame after frame
+        x, y, _ = gen.frames(pa.probabilities, pa.constellation, nm.noise_sigma, S, B, ld=ld)
+    else:
+        x = draw_symbols(p, S, ld, gen, uniform)
+        y = a[x] + nm.noise_sigma * torch.randn((S, ld), generator=gen, device=device, dtype=torch.float64)
+    lappr = torch.empty((S * bps, ld), dtype=torch.float64, device=device)
+    if mode == "softening":                            # reconciliation.pyx:129-145
+        _, nhat, word = nm.bob_map_device(y, B)
+        if check_demapper(demapper) == "simplified":   # noisemapper.pyx:605-620 in place of :544-559
+            nm.demap_simplified_device(nhat, x, B, alpha, out=lappr)
+        else:
+            nm.demap_device(nhat, x, B, alpha, out=lappr)
+    elif mode == "direct":                             # reconciliation.pyx:209-221
+        if two_variance is None:
+            raise ValueError("the direct mode needs two_variance")
+        word = torch.empty((S * bps, ld), dtype=torch.uint8, device=device)
+        _lib.check(_lib.load().qr_symbols_to_bits_device(bps, B, ld, S, dptr(x), dptr(word), sp), "symbols_to_bits")
+        _lib.check(_lib.load().qr_direct_lappr_device(nm.handle, float(two_variance), B, ld, S, dptr(y), dptr(lappr), sp),
+                   "direct_lappr")
+    else:                                              # reconciliation.pyx:290-303
+        _, _, word = nm.bob_map_device(y, B)
+        table = torch.tensor(np.ascontiguousarray(nm.bare_llr_table), dtype=torch.float64, device=device)
+        _lib.check(_lib.load().qr_bare_llr_device(bps, dptr(table), B, ld, S, dptr(x), dptr(lappr), sp), "bare_llr")
+    return lappr, word
+
+
 class Simulator:
     def __init__(self, decoder: Decoder, bps: int, mode: str = "softening", max_iterations: int = 50,
                  alpha: float = 1.0, batch: int = 4096, configuration_base: bool = False, step: float = 2.0,
@@ -74,60 +126,16 @@ class Simulator:
         self.cfg = np.zeros(self.pa.order, np.uint8) if configuration_base else alternating_config(self.pa.order)
         self.device = torch.device("cuda", device)
         self._dev_index = device
-        self._a = torch.tensor(self.pa.constellation, dtype=torch.float64, device=self.device)
-        self._p = torch.tensor(self.pa.probabilities, dtype=torch.float64, device=self.device)
-        self._uniform = bool(np.all(self.pa.probabilities == self.pa.probabilities[0]))
+        self._tables = source_tables(self.pa, self.device)
 
     # ---------------------------------------------------------------- pieces
-    def _stream(self):
-        return stream_arg(None, self.device)[1]
-
-    def _symbols(self, S, ld, gen):
-        return draw_symbols(self._p, S, ld, gen, self._uniform)
-
-    def _bits(self, x, B, ld):
-        import torch
-
-        w = torch.empty((self.S * self.pa.bit_per_symbol, ld), dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.load().qr_symbols_to_bits_device(self.pa.bit_per_symbol, B, ld, self.S, dptr(x), dptr(w),
-                                                         self._stream()), "symbols_to_bits")
-        return w
-
-    def _synd(self, word, B, ld):
-        return syndrome_device(self.dec, word, B, ld)
-
     def frames(self, nm: NoiseMapper, B: int, gen, two_variance: float):
         """One batch of inputs for the selected mode: (lappr [V, ld], synd [C, ld], word [V, ld], ld).
         gen: a torch generator, or the NumpyStream the frames are drawn from (stream="numpy")."""
-        import torch
-
         ld = leading_dim(B)
-        S = self.S
-        if self.stream == "numpy":                         # reconciliation.pyx:129-132, frame after frame
-            x, y, _ = gen.frames(self.pa.probabilities, self.pa.constellation, nm.noise_sigma, S, B, ld=ld)
-        else:
-            x = self._symbols(S, ld, gen)
-            y = self._a[x] + nm.noise_sigma * torch.randn((S, ld), generator=gen, device=self.device,
-                                                          dtype=torch.float64)
-        lappr = torch.empty((self.V, ld), dtype=torch.float64, device=self.device)
-        if self.mode == "softening":                       # reconciliation.pyx:129-145
-            _, nhat, word = nm.bob_map_device(y, B)
-            synd = self._synd(word, B, ld)
-            if self.demapper == "simplified":          # noisemapper.pyx:605-620 in place of :544-559
-                nm.demap_simplified_device(nhat, x, B, self.alpha, out=lappr)
-            else:
-                nm.demap_device(nhat, x, B, self.alpha, out=lappr)
-        elif self.mode == "direct":                        # reconciliation.pyx:209-221
-            word = self._bits(x, B, ld)
-            synd = self._synd(word, B, ld)
-            _lib.check(_lib.load().qr_direct_lappr_device(nm.handle, float(two_variance), B, ld, S, dptr(y), dptr(lappr),
-                                                          self._stream()), "direct_lappr")
-        else:                                              # reconciliation.pyx:290-303
-            xh, _, word = nm.bob_map_device(y, B)
-            synd = self._synd(word, B, ld)
-            table = torch.tensor(np.ascontiguousarray(nm.bare_llr_table), dtype=torch.float64, device=self.device)
-            _lib.check(_lib.load().qr_bare_llr_device(self.pa.bit_per_symbol, dptr(table), B, ld, S, dptr(x), dptr(lappr),
-                                                      self._stream()), "bare_llr")
+        lappr, word = llr_source(nm, self.pa, self.S, B, gen, self.mode, self.demapper, self.alpha, two_variance,
+                                 self.stream, self._tables)
+        synd = syndrome_device(self.dec, word, B, ld)
         return lappr, synd, word, ld
 
     # ------------------------------------------------------------------ run
