@@ -24,6 +24,12 @@
  *    B <= ld and ld a multiple of 64 (one wavefront = 64 frames).  They are
  *    asynchronous on `stream` (a hipStream_t; NULL = the null stream), make no
  *    allocation and no host synchronisation (graph-capturable).
+ *  - A caller's device workspace (d_workspace of qr_decode_batch_device, qr_decode_frames_device,
+ *    qr_mi_montecarlo_device, qr_lappr_info_device, qr_npstream_frames_device) must be 256-byte
+ *    aligned: the arrays inside it are placed at 256-byte steps from its base.  A misaligned base
+ *    is QR_EVALUE before any launch.  The library writes nothing outside
+ *    [d_workspace, d_workspace + the size its *_workspace_size returned), and reads nothing inside
+ *    it that the same call has not written: what the workspace holds on entry never matters.
  *  - All arithmetic is IEEE fp64, unfused, in the reference's operation order.
  */
 #ifndef QAMR_H

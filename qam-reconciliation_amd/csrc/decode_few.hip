@@ -318,6 +318,7 @@ int decode_frames_device(const qr_code *code, int B, const double *lappr, const 
     if (B <= 0 || B > INT32_MAX - kWave) return set_error(QR_EVALUE, "decode: B must be positive (B=%d)", B);
     if (!lappr || !synd || !final_post || !success || !iters || !ws_ptr)
         return set_error(QR_EVALUE, "decode: null pointer argument");
+    if (!ws_aligned(ws_ptr)) return set_error(QR_EVALUE, "decode: workspace must be 256-byte aligned");
     DeviceGuard dg(code->device);
     if (few_route(code, B, max_it)) {
         const size_t need = few_layout(code, B, max_it).bytes;

@@ -1152,6 +1152,7 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
         return set_error(QR_EVALUE, "decode: need 0 < B <= ld and ld %% 64 == 0 (B=%d, ld=%d)", B, ld);
     if (!lappr || !synd || !final_post || !success || !iters || !ws_ptr)
         return set_error(QR_EVALUE, "decode: null pointer argument");
+    if (!ws_aligned(ws_ptr)) return set_error(QR_EVALUE, "decode: workspace must be 256-byte aligned");
     const DecodeWs w = ws_layout(code, ld, max_it, ws_ptr, ws_size);
     if (ws_size < w.base_bytes)
         return set_error(QR_EVALUE, "decode: workspace too small (%zu < %zu)", ws_size, w.base_bytes);

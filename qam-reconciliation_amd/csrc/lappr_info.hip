@@ -236,6 +236,7 @@ int qr_lappr_info_device(int32_t bps, int32_t B, int32_t ld, int64_t S, const do
     if (!d_workspace || workspace_bytes < need)
         return set_error(QR_EVALUE, "workspace too small: %zu bytes, need %zu (qr_lappr_info_workspace_size)", workspace_bytes,
                          need);
+    if (!ws_aligned(d_workspace)) return set_error(QR_EVALUE, "workspace must be 256-byte aligned");
     int device = 0;   // no handle: the caller's current device, as the other handle-free *_device entries
     QR_HIP(hipGetDevice(&device));
     return info_launch(device, bps, B, ld, S, d_lappr, d_word, A, al, d_loss, d_errors, d_total, d_total_errors, d_workspace,

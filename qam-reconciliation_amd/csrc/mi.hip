@@ -396,6 +396,7 @@ int qr_mi_montecarlo_device(const qr_demap *dm, uint32_t which_mask, int32_t B, 
         if (!d_workspace || workspace_bytes < need)
             return set_error(QR_EVALUE, "workspace too small: %zu bytes, need %zu (qr_mi_workspace_size)", workspace_bytes,
                              need);
+        if (!ws_aligned(d_workspace)) return set_error(QR_EVALUE, "workspace must be 256-byte aligned");
         d_terms = (double *)d_workspace;
     }
     DeviceGuard g(dm->device);

@@ -55,8 +55,12 @@ inline bool dispatch_int_seq(int v, F &f, std::integer_sequence<int, I...>) {
     return ((v == LO + I && (f(std::integral_constant<int, LO + I>{}), true)) || ...);
 }
 
-// Bump cursor over a device buffer: take<T>(n) is the next n elements of T, 256-byte aligned.
+// Bump cursor over a device buffer: take<T>(n) is the next n elements of T, 256-byte aligned
+// from a 256-byte aligned base (ws_aligned: what every entry requires of a caller's workspace;
+// hipMalloc's blocks, and so Scratch's, are).
 // With a null base it only measures: every take is null and off counts the bytes walked.
+inline bool ws_aligned(const void *p) { return ((uintptr_t)p & 255) == 0; }
+
 struct Cursor {
     uintptr_t base;
     size_t off = 0;

@@ -18,6 +18,7 @@ from conftest import assert_bit_exact
 
 import oracle as O
 from decode_fixture import himix_code, knobs, scattered_code
+from workspace_fixture import decode_ws_map, graph_counts, map_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -60,17 +61,13 @@ def test_high_degree_checks_vs_oracle(gpu, split):
 
 
 def _workspace_closed_form(vid, cid, ld, max_it, repack):
-    """The decode workspace's size restated from the code's counts (decoder.hip ws_layout)."""
-    A = lambda n: -(-n // 256) * 256
-    E, V, C = vid.size, int(vid.max()) + 1, int(cid.max()) + 1
-    dc, dv = np.bincount(cid), np.bincount(vid)
-    classes = np.unique(dc)
-    fb_rows = int(sum(int((dc == d).sum()) * (int(d) - 2) for d in classes if d > 16))  # runtime-degree classes
-    iter_code = len(classes) == 1 and 2 <= classes[0] <= 10 and dv.max() <= 64 and 8 * E * ld <= 1 << 30
-    base = (A(8 * E * ld) * (2 if iter_code else 1) + A(ld) + A((max(max_it, 0) + 2) * ld) + A(8 * fb_rows * ld) +
-            A(4 * ld) + 256)
-    work_set = 3 * A(8 * V * ld) + 2 * A(C * ld) + A(8 * E * ld) + A(4 * ld)
-    return base + (work_set if repack and ld % 512 == 0 else 0), fb_rows, iter_code
+    """The decode workspace's size: the sum of the layout restated array by array in
+    tests/workspace_fixture.py decode_ws_map (decoder.hip ws_layout), which the workspace-contract
+    tests fill by; tests/test_workspace_cpu.py holds that sum to the closed form in the code's
+    counts.  -> (bytes, F-scratch rows, second message buffer present)."""
+    m = decode_ws_map(vid, cid, ld, max_it, repack)
+    names = [e[0] for e in m]
+    return map_bytes(m), graph_counts(vid, cid)[3], "c2v2" in names
 
 
 def test_workspace_bytes_closed_form(gpu):

@@ -15,6 +15,7 @@ import pytest
 from conftest import assert_bit_exact
 
 import lappr_info_fixture as F
+import workspace_fixture as W
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +29,16 @@ def pool(obps, snr_db, n):
     return L.reshape(n, obps), w.reshape(n, obps)
 
 
-def frames(bps, S, B, seed):
-    """B frames of S symbols drawn from the pool, the specials planted -> (lappr [B, S * bps], word [B, S * bps])."""
+def frames(bps, S, B, seed, plant=True):
+    """B frames of S symbols drawn from the pool, the specials planted (unless plant is false)
+    -> (lappr [B, S * bps], word [B, S * bps])."""
     obps, snr, n = POOL[bps]
     pL, pw = pool(obps, snr, n)
     per = bps // obps
     idx = np.random.default_rng(seed).integers(0, n, (B, S * per))
     L = np.ascontiguousarray(pL[idx].reshape(B, S * bps))
     w = np.ascontiguousarray(pw[idx].reshape(B, S * bps))
-    return F.plant_specials(L, bps), w
+    return (F.plant_specials(L, bps) if plant else L), w
 
 
 def to_fi(a, ld, fill):
@@ -49,9 +51,21 @@ def to_fi(a, ld, fill):
     return t
 
 
-def run_raw(L, w, bps, alphas, ld):
+def info_ws_map(bps, ld, S, A):
+    """The workspace of qr_lappr_info_device (lappr_info.hip info_workspace) in the form of
+    workspace_fixture.decode_ws_map: the chunk sums wloss [A][bps][chunks][ld] fp64, then the chunk error
+    counts werr [bps][chunks][ld] int32.  Both are summed and never used as indices, so any value is in range;
+    the typed fill gives werr the "index" pattern, a wrong count."""
+    rows = bps * -(-S // 256) * ld
+    n0 = W.A256(8 * A * rows)
+    return [("wloss", 0, n0, "f64"), ("werr", n0, W.A256(4 * rows), "index")]
+
+
+def run_raw(L, w, bps, alphas, ld, fill="typed", donor=None):
     """qr_lappr_info_device on its own buffers: NaN LAPPRs and bits of 255 in the padding columns, every output
-    one row longer than the interface says and pre-filled with a pad value -> the four padded host arrays."""
+    one row longer than the interface says and pre-filled with a pad value -> the four padded host arrays.  The
+    workspace lies between two guards and holds the given fill (tests/workspace_fixture.py) when the call
+    starts; ``run_raw.last_view`` is the workspace view afterwards (a donor for "leftover")."""
     import torch
 
     from qamr import _lib
@@ -67,15 +81,21 @@ def run_raw(L, w, bps, alphas, ld):
     lib = _lib.load()
     need = C.c_size_t(0)
     _lib.check(lib.qr_lappr_info_workspace_size(bps, ld, S, A, C.byref(need)))
-    ws = torch.empty(need.value + 256, dtype=torch.uint8, device="cuda")
-    ws[need.value:] = 0xA5
+    m = info_ws_map(bps, ld, S, A)
+    assert W.map_bytes(m) == need.value
+    guard = W.guard_bytes(ld)
+    whole, ws = W.guarded(need.value, guard)
+    W.fill(ws, fill, m, ld, donor)
     al = np.ascontiguousarray(alphas, np.float64)
     _lib.check(lib.qr_lappr_info_device(bps, B, ld, S, dptr(Lt), dptr(wt), A, _lib.ptr(al), dptr(loss), dptr(errors),
                                         dptr(total), dptr(terr), dptr(ws), need.value,
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    assert bool((ws[need.value:] == 0xA5).all()), "the kernels wrote past the workspace they asked for"
-    return loss.cpu().numpy(), errors.cpu().numpy(), total.cpu().numpy(), terr.cpu().numpy()
+    W.assert_guards(whole, guard, need.value, "qr_lappr_info_device")
+    run_raw.last_view = ws
+    got = loss.cpu().numpy(), errors.cpu().numpy(), total.cpu().numpy(), terr.cpu().numpy()
+    W.assert_no_fill_payload(got[0], "loss")
+    W.assert_no_fill_payload(got[2], "total")
+    return got
 
 
 def check_against(ref, got, A, bps, B, ld):
@@ -94,6 +114,10 @@ def check_against(ref, got, A, bps, B, ld):
 # (S, bps, B, A): every S, bps, B and A of the issue's lists; at most 4.0e5 terms (S bps B A) per case
 CASES = [(1, 1, 1, 1), (255, 2, 3, 3), (256, 4, 64, 1), (257, 8, 65, 3), (513, 2, 3, 16), (513, 1, 64, 3),
          (256, 2, 1, 16), (257, 4, 3, 3), (255, 8, 64, 1), (1, 8, 65, 3), (513, 4, 65, 1), (255, 1, 65, 16)]
+# k_lappr_info_total walks the frames in passes of 1024 and reuses its LDS array between them: B = 1025 is one
+# frame into the second pass, B = 2049 one into the third
+PASS_CASES = [(1, 1, 1025, 1), (3, 2, 2049, 3)]
+CASES += PASS_CASES
 
 
 @pytest.mark.parametrize("S,bps,B,A", CASES)
@@ -101,13 +125,26 @@ def test_bit_exact_against_the_evaluator(gpu, S, bps, B, A):
     assert S * bps * B * A <= 4.02e5
     L, w = frames(bps, S, B, 7000 + S + 10 * bps + B)
     alphas = F.SCALES[:A] if A > 1 else ((1.0,) if S != 256 else (0.5,))
-    ld = 64 if B <= 64 else 128
+    ld = -(-B // 64) * 64
     ref = F.evaluate(L, w, bps, alphas)
     n_special = int((~np.isfinite(ref[0])).sum())
     got = run_raw(L, w, bps, alphas, ld)
     check_against(ref, got, A, bps, B, ld)
     if S * bps >= len(F.SPECIALS):   # the planted inf / NaN reach the sums of the first and of the last frame
         assert n_special > 0 and not np.isfinite(ref[0][:, :, B - 1]).all()
+
+
+@pytest.mark.parametrize("S,bps,B,A", PASS_CASES)
+def test_totals_past_one_pass_on_finite_frames(gpu, S, bps, B, A):
+    """The shapes of PASS_CASES without the planted specials (which put an inf or a NaN into the totals of the
+    case above from the first or the last frame on, whatever the later passes add): every total is finite, so
+    each pass's partial sum and the order of the chain over all B frames show in its last bits."""
+    L, w = frames(bps, S, B, 7100 + B, plant=False)
+    alphas = F.SCALES[:A] if A > 1 else (1.0,)
+    ld = -(-B // 64) * 64
+    ref = F.evaluate(L, w, bps, alphas)
+    assert np.isfinite(ref[0]).all() and np.isfinite(ref[2]).all() and (ref[2] > 0).all()
+    check_against(ref, run_raw(L, w, bps, alphas, ld), A, bps, B, ld)
 
 
 def test_python_wrapper_equals_raw_entry(gpu):

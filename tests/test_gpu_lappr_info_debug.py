@@ -14,5 +14,5 @@ CASES = [f"{FILE}::test_bit_exact_against_the_evaluator", f"{FILE}::test_stream_
 
 
 def test_lappr_info_debug_build_device_checks(gpu):
-    # the 12 shapes, the replay
-    rerun_on_debug_build(CASES, 13, timeout=300)
+    # the 14 shapes (two of them past one pass of k_lappr_info_total), the replay
+    rerun_on_debug_build(CASES, 15, timeout=300)
