@@ -25,7 +25,7 @@
  *    asynchronous on `stream` (a hipStream_t; NULL = the null stream), make no
  *    allocation and no host synchronisation (graph-capturable).
  *  - A caller's device workspace (d_workspace of qr_decode_batch_device, qr_decode_frames_device,
- *    qr_mi_montecarlo_device, qr_lappr_info_device, qr_npstream_frames_device) must be 256-byte
+ *    qr_decode_layered_device, qr_mi_montecarlo_device, qr_lappr_info_device, qr_npstream_frames_device) must be 256-byte
  *    aligned: the arrays inside it are placed at 256-byte steps from its base.  A misaligned base
  *    is QR_EVALUE before any launch.  The library writes nothing outside
  *    [d_workspace, d_workspace + the size its *_workspace_size returned), and reads nothing inside
@@ -74,7 +74,8 @@ QR_API int qr_profile_select(const char *names);
 /* name: "check" (one check sweep, all degree classes), "check_d<D>" (the launch
  * for check degree D), "check1" (first sweep), "var", "var_init", "status",
  * "parity", "demap", "demap_interp", "bob", "syndrome", "count"; the few-frame schedule:
- * "few_check" (every check-sweep launch), "few_var", "few_var_init"; numpy's stream: "np_words",
+ * "few_check" (every check-sweep launch), "few_var", "few_var_init"; the layered schedule:
+ * "layer_check" (every layer launch), "layer_check_d<D>", "layer_parity"; numpy's stream: "np_words",
  * "np_scan", "np_chain", "np_fill".  Synchronises pending events. */
 QR_API int qr_profile_query(const char *name, double *total_ms, int64_t *launches);
 
@@ -173,6 +174,60 @@ QR_API int qr_decode_frames_device(const qr_code *code, int32_t B, const double 
  * on the handle's scratch, device-to-host copies. */
 QR_API int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, const uint8_t *synd, int32_t max_iterations,
                    double *final_lappr, uint8_t *success, int32_t *iterations);
+
+/* ------------------------------------------------- layered decode schedule */
+/* A layered (serial-check) sum-product schedule.  The reference has none: this library defines
+ * it, and the entries below are bit-exact against the definition.  The posteriors are updated
+ * after every check instead of after a whole sweep, so the later checks of an iteration see the
+ * earlier checks' messages; the box-plus and the F/B recursion are the flooding decoder's
+ * (decoder.pyx:322-369, :41-45), IEEE fp64, unfused, glibc exp/log.  Per frame:
+ *
+ *   if check_lappr(lappr, synd): return (1, 0, copy of lappr)              (decoder.pyx:400-405)
+ *   post[v] = lappr[v] + 0.0 for every v with an edge, lappr[v] otherwise
+ *   c2v[e]  = 0.0
+ *   for it in 0 .. max_iterations-1:
+ *       for c in schedule order:
+ *           edges e_0..e_{d-1} of c in ascending edge id, variables v_i
+ *           old_i = c2v[e_i];  m_i = post[v_i] - old_i                     (all i, before any write)
+ *           new_0..new_{d-1} = the reference's check rule on m with the syndrome sign
+ *           for i ascending:  post[v_i] = (post[v_i] - old_i) + new_i;  c2v[e_i] = new_i
+ *       if check_lappr(post, synd): return (1, it+1, post)                 (decoder.pyx:431-433)
+ *   return (0, max_iterations, post)
+ *
+ * post[v_i] in the update line is read again: a check that holds a variable twice (parallel
+ * edges) updates it twice, the second edge from what the first left.  A frame that has stopped is
+ * not touched again; max_iterations = 0 gives (0, 0, post) after the init line.
+ * Schedule order: by (layer_of[c], c), where layer_of[c] is the smallest l >= 0 such that no check
+ * c' < c with layer_of[c'] = l shares a variable with c (first-fit in ascending check id).  The
+ * checks of one layer share no variable, so the order within a layer does not change a bit. */
+
+/* The layers of a code: *n_layers, and layer_of[C] (or NULL). */
+QR_API int qr_code_layers(const qr_code *code, int32_t *n_layers, int32_t *layer_of);
+
+/* Device workspace (bytes) of qr_decode_layered_device at leading dim ld and max_iterations (edge
+ * messages E*ld fp64 + per-frame flags).  A negative max_iterations is QR_EVALUE. */
+QR_API int qr_decode_layered_workspace_size(const qr_code *code, int32_t ld, int32_t max_iterations, size_t *bytes);
+
+/* The layered decode of B independent frames; layouts and error rules as qr_decode_batch_device
+ * (0 < B <= ld, ld % 64 == 0, a 256-byte aligned workspace of at least the size above, no null
+ * pointer; else QR_EVALUE before any launch), and a negative max_iterations is QR_EVALUE too.  A
+ * code with a check degree above 16 is QR_EUNSUPPORTED before any launch.
+ *   d_final [V][ld] fp64   the posteriors, updated in place while the decode runs; at the end the
+ *                          final LAPPRs of the definition; the padding columns [B, ld) are not written
+ *   d_success[B], d_iters[B]: the (success, iterations) pair of every frame.
+ * One launch per non-empty (layer, check degree) in schedule order, then per iteration a syndrome
+ * test of the posteriors and the status update, all on `stream`: the kernel boundary is the only
+ * synchronisation between layers.  Asynchronous, no allocation, every data-dependent decision on
+ * the device: capturable into a HIP graph (a linear one; no second stream). */
+QR_API int qr_decode_layered_device(const qr_code *code, int32_t B, int32_t ld, const double *d_lappr,
+                                    const uint8_t *d_synd, int32_t max_iterations, double *d_final, uint8_t *d_success,
+                                    int32_t *d_iters, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The layered decode of B frames from host memory, frame-major: lappr[B][V], synd[B][C],
+ * final[B][V]: copies to the handle's scratch, transposed there into ld = B rounded up to 64,
+ * qr_decode_layered_device, transposed and copied back. */
+QR_API int qr_decode_layered_host(const qr_code *code, int32_t B, const double *lappr, const uint8_t *synd,
+                                  int32_t max_iterations, double *final_lappr, uint8_t *success, int32_t *iterations);
 
 /* --------------------------------------------- Decoder unit-test surface */
 /* Every *_host entry that takes n elements from host arrays follows one rule: a null handle is

@@ -85,6 +85,8 @@ static int free_code(qr_code *c) {
     (void)hipFree(c->d_var_edge);
     (void)hipFree(c->d_var_msg);
     (void)hipFree(c->d_gtab);
+    (void)hipFree(c->d_layer_checks);
+    (void)hipFree(c->d_chk_repeat);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->s2) (void)hipStreamDestroy(c->s2);
@@ -157,6 +159,18 @@ int qr_code_create(const int64_t *e_to_v, const int64_t *e_to_c, int64_t nv, int
         std::vector<GlibcTables> gt(1);
         build_glibc_tables(&gt[0]);
         if ((rc = upload(&code->d_gtab, gt))) {
+            free_code(code);
+            return rc;
+        }
+    }
+    {
+        // the layered schedule's layers and check lists (decode_layered.hip), uploaded once
+        Layers lay;
+        build_layers(T, lay);
+        code->n_layers = lay.n_layers;
+        code->layer_of = lay.layer_of;
+        for (const LayerSeg &g : lay.segs) code->layer_segs.push_back(LayerSegDev{g.layer, g.degree, g.off, g.n});
+        if ((rc = upload(&code->d_layer_checks, lay.checks)) || (rc = upload(&code->d_chk_repeat, lay.repeat))) {
             free_code(code);
             return rc;
         }
@@ -260,6 +274,63 @@ int qr_decode_frames_device(const qr_code *code, int32_t B, const double *d_lapp
     if (!code) return set_error(QR_EVALUE, "null code");
     return decode_frames_device(code, B, d_lappr, d_synd, max_it, d_final, d_success, d_iters, ws, ws_size,
                                 (hipStream_t)stream);
+}
+
+int qr_code_layers(const qr_code *code, int32_t *n_layers, int32_t *layer_of) {
+    if (!code) return set_error(QR_EVALUE, "null code");
+    if (n_layers) *n_layers = code->n_layers;
+    if (layer_of) std::copy(code->layer_of.begin(), code->layer_of.end(), layer_of);
+    return QR_OK;
+}
+
+int qr_decode_layered_workspace_size(const qr_code *code, int32_t ld, int32_t max_it, size_t *bytes) {
+    if (!code || !bytes) return set_error(QR_EVALUE, "null argument");
+    if (ld <= 0 || ld % kWave) return set_error(QR_EVALUE, "ld must be a positive multiple of 64");
+    if (max_it < 0) return set_error(QR_EVALUE, "max_iterations must not be negative");
+    *bytes = layered_ws_bytes(code, ld, max_it);
+    return QR_OK;
+}
+
+int qr_decode_layered_device(const qr_code *code, int32_t B, int32_t ld, const double *d_lappr, const uint8_t *d_synd,
+                             int32_t max_it, double *d_final, uint8_t *d_success, int32_t *d_iters, void *ws,
+                             size_t ws_size, void *stream) {
+    if (!code) return set_error(QR_EVALUE, "null code");
+    return decode_layered_device(code, B, ld, d_lappr, d_synd, max_it, d_final, d_success, d_iters, ws, ws_size,
+                                 (hipStream_t)stream);
+}
+
+// Frame-major host arrays: transposed on the device into ld = B rounded up to the wavefront,
+// decoded there, transposed back (the handle's scratch holds the staging and the workspace).
+int qr_decode_layered_host(const qr_code *code, int32_t B, const double *lappr, const uint8_t *synd, int32_t max_it,
+                           double *final_lappr, uint8_t *success, int32_t *iterations) {
+    if (!code) return set_error(QR_EVALUE, "null code");
+    if (B <= 0 || B > INT32_MAX - kWave) return set_error(QR_EVALUE, "B must be positive");
+    if (max_it < 0) return set_error(QR_EVALUE, "max_iterations must not be negative");
+    if (int rc = check_host_arrays(B, lappr, synd, final_lappr, success, iterations)) return rc;
+    if (code->max_dc > kMaxTemplDeg)
+        return set_error(QR_EUNSUPPORTED, "layered decode: check degree %d above %d", code->max_dc, kMaxTemplDeg);
+    const size_t V = code->V, C = code->C, nB = (size_t)B;
+    const int ld = (int)align_up(nB, kWave);
+    const size_t wsb = layered_ws_bytes(code, ld, max_it);
+    HostTrip t(code->scratch, code->device);
+    double *d_fm, *d_lfi, *d_ffi;  // d_fm: the frame-major LAPPRs in, then the frame-major result out
+    uint8_t *d_sfm, *d_sfi, *d_succ;
+    int32_t *d_it;
+    char *d_ws;
+    if (!t.take(&d_fm, V * nB, &d_lfi, V * ld, &d_ffi, V * ld, &d_sfm, C * nB, &d_sfi, C * ld, &d_succ, nB, &d_it, nB,
+                &d_ws, wsb))
+        return t.rc;
+    t.up(d_fm, lappr, V * nB);
+    t.up(d_sfm, synd, C * nB);
+    hipStream_t s = nullptr;
+    if (t.ok()) t.rc = launch_transpose_to_fi_f64(B, ld, (int64_t)V, d_fm, d_lfi, s);
+    if (t.ok()) t.rc = launch_transpose_to_fi_u8(B, ld, (int64_t)C, d_sfm, d_sfi, s);
+    if (t.ok()) t.rc = decode_layered_device(code, B, ld, d_lfi, d_sfi, max_it, d_ffi, d_succ, d_it, d_ws, wsb, s);
+    if (t.ok()) t.rc = launch_transpose_to_fm_f64(B, ld, (int64_t)V, d_ffi, d_fm, s);
+    t.down(final_lappr, d_fm, V * nB);
+    t.down(success, d_succ, nB);
+    t.down(iterations, d_it, nB);
+    return t.rc;
 }
 
 int qr_decode_host(const qr_code *code, int32_t B, const double *lappr, const uint8_t *synd, int32_t max_it,

@@ -1,5 +1,5 @@
 // decode_dev.hpp -- what the decoder's units (decoder.hip, decode_repack.hip, decode_small.hip,
-// decode_few.hip, decode_api.hip) share on the device side: the check modes, the debug sites, the
+// decode_few.hip, decode_layered.hip, decode_api.hip) share on the device side: the check modes, the debug sites, the
 // accessors of the frame-innermost arrays, the RangeSel fields, the packed / templated degree
 // bounds with their host-side dispatch.  Included by .hip files only.
 #pragma once
@@ -26,6 +26,11 @@ enum DebugSite {
     kDbgFewCheck = 17,     // few-frame check sweep: lane -> (class, check): check id or its degree
     kDbgFewPost = 18,      // few-frame check sweep: gathered posterior index outside [0, V)
     kDbgFewSlot = 19,      // few-frame sweeps: message slot outside [0, E)
+    // 20..24: npstream.hip (NpDebugSite); 25, 26: lappr_info.hip (InfoDebugSite)
+    kDbgLayCheck = 27,     // layered check sweep: check id outside [0, C) or not of the launch's degree
+    kDbgLayVar = 28,       // layered check sweep: variable outside [0, V)
+    kDbgLayEdge = 29,      // layered check sweep: edge (message row) outside [0, E)
+    kDbgLayFrame = 30,     // layered check sweep: frame column outside [0, ld)
 };
 
 // Check-node arithmetic: the reference's box-plus bit for bit -- glibc exp/log restated

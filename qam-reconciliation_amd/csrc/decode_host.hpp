@@ -2,7 +2,7 @@
 // workspace helpers, and the declarations of what one unit calls in another (decoder.hip: the
 // frame-parallel schedules and the status kernels; decode_repack.hip: the column repack;
 // decode_small.hip: k_iter and k_resident; decode_few.hip: the few-frame schedule and the
-// frame-major route; decode_api.hip: the C entry points).
+// frame-major route; decode_layered.hip: the layered schedule; decode_api.hip: the C entry points).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -51,6 +51,23 @@ int launch_init_status(int B, int ld, uint8_t *active, uint8_t *success, int32_t
                        int w0, int w1, hipStream_t s);
 int launch_status(int f0, int f1, int t, int final_call, int32_t final_iters, const uint8_t *unsat_t, uint8_t *active,
                   uint8_t *success, int32_t *iters, const int32_t *sel, const int32_t *fid, hipStream_t s);
+
+// The two sweeps of the flooding decode that the layered schedule (decode_layered.hip) reuses, over
+// all ld columns with no active-frame list: the parity-only check sweep of `post` (k_check
+// <kParityOnly>: unsat[f] = 1 for every running frame with an unsatisfied check; unsat zeroed by
+// the caller) and the init variable sweep (k_var<true>: post = lappr + 0.0, a plain copy for
+// frames that stopped at iteration 0; columns [B, ld) not written).  counts: the caller's
+// 256-byte count block (k_init_status has set it).
+int launch_parity_sweep(const qr_code *code, int B, int ld, const double *post, const uint8_t *synd,
+                        const uint8_t *active, uint8_t *unsat, int32_t *counts, hipStream_t s);
+int launch_var_init(const qr_code *code, int B, int ld, const double *lappr, double *post, const uint8_t *active,
+                    int32_t *counts, hipStream_t s);
+
+// ---- decode_layered.hip: the layered (serial-check) schedule
+size_t layered_ws_bytes(const qr_code *code, int ld, int max_it);
+int decode_layered_device(const qr_code *code, int B, int ld, const double *lappr, const uint8_t *synd, int max_it,
+                          double *final_post, uint8_t *success, int32_t *iters, void *ws_ptr, size_t ws_size,
+                          hipStream_t s);
 
 // ---- decode_repack.hip: the two launches of the column repack (run_split2 fills the arguments)
 struct RepackArgs {

@@ -28,7 +28,8 @@
 // (run_flat); small codes with one launch per iteration (run_iter) or one launch
 // per decode with a workgroup per frame and its messages in LDS (k_resident), both in
 // decode_small.hip.  The column repack's kernels: decode_repack.hip.  A few frames on frame-major
-// arrays (decode_frames_device, qr_decode_host): decode_few.hip.  The C entry points: decode_api.hip.
+// arrays (decode_frames_device, qr_decode_host): decode_few.hip.  The layered (serial-check)
+// schedule, which reuses this unit's parity-only and init sweeps: decode_layered.hip.  The C entry points: decode_api.hip.
 // This unit: the frame-parallel check and variable sweeps, the status and compaction kernels,
 // the workspace layout and the launch layer of run_flat and run_split2.
 #include "debug_check.hpp"
@@ -1216,6 +1217,30 @@ int decode_batch_device(const qr_code *code, int B, int ld, const double *lappr,
     }
     if ((rc = launch_status(P, 0, ld, tf, 1, max_it, unsat_last))) return rc;
     return QR_OK;
+}
+
+// A plan over the caller's arrays alone (no message buffer, lists or work set): what the two
+// sweeps below read.  counts: a count block (its finite flag's address travels in the arguments;
+// neither sweep reads it).
+static Plan bare_plan(const qr_code *code, int B, int ld, const double *lappr, const uint8_t *synd, double *post,
+                      const uint8_t *active, int32_t *counts, hipStream_t s) {
+    DecodeWs w{};
+    w.active = const_cast<uint8_t *>(active);
+    w.acount = counts;
+    w.rsel = counts + 4;
+    return Plan{code, B, ld, lappr, synd, post, nullptr, nullptr, w, g_tune.nt.load() != 0, s};
+}
+
+int launch_parity_sweep(const qr_code *code, int B, int ld, const double *post, const uint8_t *synd,
+                        const uint8_t *active, uint8_t *unsat, int32_t *counts, hipStream_t s) {
+    const Plan P = bare_plan(code, B, ld, nullptr, synd, nullptr, active, counts, s);
+    return launch_checks<kParityOnly>(P, post, unsat, 0, ld);
+}
+
+int launch_var_init(const qr_code *code, int B, int ld, const double *lappr, double *post, const uint8_t *active,
+                    int32_t *counts, hipStream_t s) {
+    const Plan P = bare_plan(code, B, ld, lappr, nullptr, post, active, counts, s);
+    return launch_var<true>(P, 0, ld);
 }
 
 #if QR_DEBUG_ASSERT

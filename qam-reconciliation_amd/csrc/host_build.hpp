@@ -6,6 +6,7 @@
 //                      counting sort of the edge list into int32 CSR per check and per
 //                      variable (ascending edge id), checks grouped by degree;
 //   build_few_layout   the message slots of the node-parallel decodes (frame-resident, few-frame);
+//   build_layers       the first-fit layers of the layered decode schedule and their check lists;
 //   build_demap_host   NoiseMapper.__cinit__ tables (noisemapper.pyx:103-236) plus the
 //                      Newton-start and Taylor tables of the fast root search.
 #pragma once
@@ -126,6 +127,64 @@ inline void build_few_layout(const TannerCsr &t, FewLayout &L) {
     }
     L.var_slot.resize((size_t)t.E);
     for (int64_t k = 0; k < t.E; ++k) L.var_slot[(size_t)k] = slot_of_edge[(size_t)t.var_edge[(size_t)k]];
+}
+
+// The layers of the layered (serial-check) decode schedule (decode_layered.hip), first-fit in
+// ascending check id: layer_of[c] is the smallest l >= 0 such that no check c' < c of layer l
+// shares a variable with c, so the checks of one layer touch disjoint posteriors and may run in
+// any order.  The schedule order is (layer_of[c], c).  segs lists every non-empty (layer, check
+// degree) in that order (ascending degree within a layer); its checks are checks[off, off + n),
+// ascending.  repeat[c] = 1 iff check c holds a variable more than once (parallel edges): its
+// second edge reads the posterior its first edge has just written.
+// used[l] marks the variables of layer l, so a check costs its degree per layer tried:
+// O(E layers) time, V bytes per layer.  No HIP call.
+struct LayerSeg {
+    int32_t layer, degree;
+    int64_t off, n;
+};
+struct Layers {
+    int32_t n_layers = 0;
+    std::vector<int32_t> layer_of;  // [C]
+    std::vector<uint8_t> repeat;    // [C]
+    std::vector<int32_t> checks;    // [C], by (layer, degree, check id)
+    std::vector<LayerSeg> segs;
+};
+inline void build_layers(const TannerCsr &t, Layers &L) {
+    const size_t C = (size_t)t.C;
+    L.n_layers = 0;
+    L.layer_of.assign(C, 0);
+    L.repeat.assign(C, 0);
+    L.checks.clear();
+    L.segs.clear();
+    std::vector<std::vector<uint8_t>> used;
+    std::vector<int32_t> vs;
+    for (size_t c = 0; c < C; ++c) {
+        const int32_t b = t.chk_ptr[c], e = t.chk_ptr[c + 1];
+        vs.assign(t.chk_var.begin() + b, t.chk_var.begin() + e);
+        std::sort(vs.begin(), vs.end());
+        L.repeat[c] = std::adjacent_find(vs.begin(), vs.end()) != vs.end();
+        size_t l = 0;
+        for (;; ++l) {
+            if (l == used.size()) used.emplace_back((size_t)t.V, (uint8_t)0);
+            bool free_layer = true;
+            for (int32_t k = b; k < e && free_layer; ++k) free_layer = !used[l][(size_t)t.chk_var[(size_t)k]];
+            if (free_layer) break;
+        }
+        for (int32_t k = b; k < e; ++k) used[l][(size_t)t.chk_var[(size_t)k]] = 1;
+        L.layer_of[c] = (int32_t)l;
+    }
+    L.n_layers = (int32_t)used.size();
+    // (layer, degree) -> its checks, ascending: a counting sort over the ascending check ids
+    const size_t nd = t.by_deg.size();
+    std::vector<int64_t> cnt((size_t)L.n_layers * nd + 1, 0);
+    auto key = [&](size_t c) { return (size_t)L.layer_of[c] * nd + (size_t)(t.chk_ptr[c + 1] - t.chk_ptr[c]); };
+    for (size_t c = 0; c < C; ++c) cnt[key(c) + 1]++;
+    for (size_t k = 0; k + 1 < cnt.size(); ++k) {
+        if (cnt[k + 1]) L.segs.push_back(LayerSeg{(int32_t)(k / nd), (int32_t)(k % nd), cnt[k], cnt[k + 1]});
+        cnt[k + 1] += cnt[k];
+    }
+    L.checks.resize(C);
+    for (size_t c = 0; c < C; ++c) L.checks[(size_t)cnt[key(c)]++] = (int32_t)c;
 }
 
 // NoiseMapper tables on the host (noisemapper.pyx:103-236) and the fast root search's

@@ -229,6 +229,12 @@ struct DegreeClass {
     int64_t few_base = 0;
 };
 
+// One launch of the layered schedule: the checks of one degree in one layer.
+struct LayerSegDev {
+    int32_t layer, degree;
+    int64_t off, n;
+};
+
 struct qr_code {
     int64_t E = 0, V = 0, C = 0;
     int32_t max_dc = 0, max_dv = 0;
@@ -247,6 +253,14 @@ struct qr_code {
     std::vector<DegreeClass> classes;
     int64_t fb_rows = 0;  // rows of the F scratch (sum over runtime-degree classes)
     qr::GlibcTables *d_gtab = nullptr; // strict box-plus: glibc exp/log data (glibc_math.hpp)
+    // layered schedule (host_build.hpp build_layers, decode_layered.hip): every check's layer, the
+    // non-empty (layer, degree) segments in schedule order with their ascending check ids
+    // (d_layer_checks[off, off + n)), and per check whether it repeats a variable
+    int32_t n_layers = 0;
+    std::vector<int32_t> layer_of;
+    std::vector<LayerSegDev> layer_segs;
+    int32_t *d_layer_checks = nullptr;
+    uint8_t *d_chk_repeat = nullptr;
     mutable qr::Scratch scratch;
     // two-stream schedule (decoder.hip run_split2; run_iter, decode_small.hip): a second stream for the variable
     // sweeps and the events that order the two; created on first use, guarded by mu

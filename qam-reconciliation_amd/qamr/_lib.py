@@ -45,6 +45,10 @@ SIGNATURES = {
     "qr_decode_frames_workspace_size": [vp, i32, i32, P(C.c_size_t)],
     "qr_decode_frames_device": [vp, i32, vp, vp, i32, vp, vp, vp, vp, C.c_size_t, vp],
     "qr_decode_host": [vp, i32, vp, vp, i32, vp, vp, vp],
+    "qr_code_layers": [vp, P(i32), vp],
+    "qr_decode_layered_workspace_size": [vp, i32, i32, P(C.c_size_t)],
+    "qr_decode_layered_device": [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, C.c_size_t, vp],
+    "qr_decode_layered_host": [vp, i32, vp, vp, i32, vp, vp, vp],
     "qr_check_lappr_host": [vp, vp, vp, vp, vp],
     "qr_check_word_host": [vp, vp, vp, vp, vp],
     "qr_process_var_nodes_host": [vp, vp, i64, vp, vp, vp, vp],

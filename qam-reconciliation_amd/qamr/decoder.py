@@ -145,13 +145,16 @@ class Decoder:
     # ---------------------------------------------------------------- decode
     def decode(self, lappr_data, synd, max_iterations):
         """decoder.pyx:441-455 -> (success, iterations, final_lappr)."""
+        return self._decode(lappr_data, synd, max_iterations, False)
+
+    def _decode(self, lappr_data, synd, max_iterations, layered):
         l = as_buffer(lappr_data, np.float64, name="lappr_data")
         s = as_buffer(synd, np.uint8, name="synd")
         if l.size != self._V:
             raise ValueError(f"lappr has {l.size} entries, the code has {self._V} variable nodes")
         if s.size != self._C:
             raise ValueError(f"synd has {s.size} entries, the code has {self._C} check nodes")
-        succ, its, res = self.decode_batch(l[None, :], s[None, :], max_iterations)
+        succ, its, res = self._decode_batch(l[None, :], s[None, :], max_iterations, layered)
         return int(succ[0]), int(its[0]), res[0]
 
     def decode_batch(self, lappr, synd, max_iterations):
@@ -159,6 +162,9 @@ class Decoder:
 
         lappr: float64 [B, V]; synd: uint8/bool [B, C].
         Returns (success uint8[B], iterations int32[B], final float64[B, V])."""
+        return self._decode_batch(lappr, synd, max_iterations, False)
+
+    def _decode_batch(self, lappr, synd, max_iterations, layered):
         l = np.ascontiguousarray(lappr)
         s = np.ascontiguousarray(bool_as_u8(synd))
         if l.dtype != np.float64 or s.dtype != np.uint8:
@@ -171,9 +177,41 @@ class Decoder:
         out = np.empty_like(l)
         succ = np.empty(B, np.uint8)
         its = np.empty(B, np.int32)
-        check(_lib.load().qr_decode_host(self._h, B, ptr(l), ptr(s), int(max_iterations), ptr(out), ptr(succ),
-                                         ptr(its)), "decode")
+        L = _lib.load()
+        entry = L.qr_decode_layered_host if layered else L.qr_decode_host
+        check(entry(self._h, B, ptr(l), ptr(s), int(max_iterations), ptr(out), ptr(succ), ptr(its)), "decode")
         return succ, its, out
+
+    # ------------------------------------------------------- layered schedule
+    def layers(self):
+        """The layers of the layered schedule: (layer_of int32 [C], n_layers).  ``layer_of[c]`` is the
+        smallest l >= 0 such that no check c' < c of layer l shares a variable with c; the schedule
+        runs the checks by (layer_of[c], c)."""
+        n = C.c_int32()
+        layer_of = np.empty(self._C, np.int32)
+        check(_lib.load().qr_code_layers(self._h, C.byref(n), ptr(layer_of)), "layers")
+        return layer_of, int(n.value)
+
+    def decode_layered(self, lappr_data, synd, max_iterations):
+        """``decode`` with the layered (serial-check) schedule: the posteriors are updated after every
+        check, in the order of ``layers()`` (include/qamr.h states the definition; the results are
+        bit-exact against it).  -> (success, iterations, final_lappr)."""
+        return self._decode(lappr_data, synd, max_iterations, True)
+
+    def decode_layered_batch(self, lappr, synd, max_iterations):
+        """``decode_batch`` with the layered schedule."""
+        return self._decode_batch(lappr, synd, max_iterations, True)
+
+    def layered_workspace_bytes(self, ld: int, max_iterations: int) -> int:
+        n = C.c_size_t()
+        check(_lib.load().qr_decode_layered_workspace_size(self._h, int(ld), int(max_iterations), C.byref(n)))
+        return int(n.value)
+
+    def decode_layered_device(self, lappr_fi, synd_fi, B: int, max_iterations: int, final_fi=None, success=None,
+                              iters=None, stream=None):
+        """``decode_device`` with the layered schedule: same tensors, same return, asynchronous on
+        ``stream``; check degrees up to 16."""
+        return self._decode_fi(True, lappr_fi, synd_fi, B, max_iterations, final_fi, success, iters, stream)
 
     # ------------------------------------------------------- device (HBM) API
     def workspace_bytes(self, ld: int, max_iterations: int) -> int:
@@ -190,21 +228,27 @@ class Decoder:
         Every tensor must be contiguous and on this decoder's GPU (checked).
         Asynchronous on ``stream`` (default: torch's current stream).  The message
         workspace is kept per stream, so calls on different streams never share it."""
+        return self._decode_fi(False, lappr_fi, synd_fi, B, max_iterations, final_fi, success, iters, stream)
+
+    def _decode_fi(self, _layered, lappr_fi, synd_fi, B, max_iterations, final_fi, success, iters, stream):
         import torch
 
-        V, ld = check_2d(lappr_fi, "decode_device", "lappr_fi", "[V, ld]")
+        what = "decode_layered_device" if _layered else "decode_device"
+        V, ld = check_2d(lappr_fi, what, "lappr_fi", "[V, ld]")
         if V != self._V:
-            raise ValueError("decode_device: tensor shapes do not match the code")
-        check_batch(B, ld, "decode_device")
+            raise ValueError(f"{what}: tensor shapes do not match the code")
+        check_batch(B, ld, what)
         check_tensor(lappr_fi, "lappr_fi", (self._V, ld), torch.float64, self._device)
         check_tensor(synd_fi, "synd_fi", (self._C, ld), torch.uint8, self._device)
-        final_fi, success, iters = self._outputs("decode_device", B, lappr_fi, final_fi, "final_fi", (self._V, ld),
+        final_fi, success, iters = self._outputs(what, B, lappr_fi, final_fi, "final_fi", (self._V, ld),
                                                  success, iters)
         stream, sp = stream_arg(stream, lappr_fi.device)
-        ws = self._workspace(stream, self.workspace_bytes(ld, max_iterations))
-        check(_lib.load().qr_decode_batch_device(self._h, int(B), int(ld), dptr(lappr_fi), dptr(synd_fi),
-                                                 int(max_iterations), dptr(final_fi), dptr(success), dptr(iters),
-                                                 dptr(ws), ws.numel(), sp), "decode_device")
+        L = _lib.load()
+        need = self.layered_workspace_bytes(ld, max_iterations) if _layered else self.workspace_bytes(ld, max_iterations)
+        ws = self._workspace(stream, need)
+        entry = L.qr_decode_layered_device if _layered else L.qr_decode_batch_device
+        check(entry(self._h, int(B), int(ld), dptr(lappr_fi), dptr(synd_fi), int(max_iterations), dptr(final_fi),
+                    dptr(success), dptr(iters), dptr(ws), ws.numel(), sp), what)
         return final_fi, success, iters
 
     def _outputs(self, what, B, lappr, final, final_name, final_shape, success, iters):

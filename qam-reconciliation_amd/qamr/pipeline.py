@@ -11,7 +11,8 @@ stage is one HIP kernel of libqamr:
   Bob    synd = H word        (k_syndrome) :139     matrix.pyx:55-60
   Alice  lappr = alpha * demap(n_hat, x)  :143-145  (k_demap, decoder layout; or, with
          demapper="simplified", formulation 1: k_demap_interp_wave)
-  Alice  decode (k_check / k_status / k_var) :147
+  Alice  decode (k_check / k_status / k_var) :147  (or, with schedule="layered", the layered
+         schedule of this library: k_layer_check per layer, no counterpart in the reference)
   count  BER/FER/iterations   (k_count_*)  :149-157
 
 The RNG stream of this pipeline is torch's: its parity is established on the fixtures
@@ -53,6 +54,23 @@ def check_demapper(demapper: str) -> str:
     if demapper not in DEMAPPERS:
         raise ValueError(f"demapper must be one of {DEMAPPERS}, got {demapper!r}")
     return demapper
+
+
+SCHEDULES = ("flooding", "layered")
+
+
+def check_schedule(schedule: str) -> str:
+    """The decode schedule: "flooding" = the reference's (decoder.pyx:391-436, Decoder.decode_device),
+    "layered" = the posteriors updated after every check (Decoder.decode_layered_device; this
+    library's own definition, include/qamr.h: about half the iterations, other LAPPRs)."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"schedule must be one of {SCHEDULES}, got {schedule!r}")
+    return schedule
+
+
+def decode_entry(dec: Decoder, schedule: str):
+    """The device decode of a schedule (both take decode_device's arguments)."""
+    return dec.decode_layered_device if check_schedule(schedule) == "layered" else dec.decode_device
 
 
 def leading_dim(B: int) -> int:
@@ -106,8 +124,9 @@ class SofteningPipeline:
 
     def __init__(self, decoder: Decoder, bps: int, snr_db: float, batch: int, alpha: float = 1.0,
                  max_iterations: int = 50, sign_config=None, step: float = 2.0, device: int = 0,
-                 demapper: str = "search"):
+                 demapper: str = "search", schedule: str = "flooding"):
         self.demapper = check_demapper(demapper)
+        self.schedule = check_schedule(schedule)
         import torch
 
         self.dec = decoder
@@ -153,7 +172,8 @@ class SofteningPipeline:
         return self.nm.demap_device(batch.nhat, batch.x, batch.B, self.alpha, out=out)
 
     def decode(self, lappr_fi, batch: Batch, final=None, success=None, iters=None):
-        return self.dec.decode_device(lappr_fi, batch.synd, batch.B, self.max_iterations, final, success, iters)
+        return decode_entry(self.dec, self.schedule)(lappr_fi, batch.synd, batch.B, self.max_iterations, final,
+                                                     success, iters)
 
     def count(self, final_fi, batch: Batch, success, iters):
         """Accumulate {bit_errors, frame_errors, successes, iter_sum, frames}."""

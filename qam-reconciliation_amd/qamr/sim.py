@@ -34,8 +34,8 @@ from ._lib import dptr, stream_arg
 from .alphabet import PAMAlphabet
 from .decoder import Decoder
 from .noisemapper import NoiseMapper
-from .pipeline import (alternating_config, check_demapper, count_errors_device, draw_symbols, leading_dim,
-                       syndrome_device)
+from .pipeline import (alternating_config, check_demapper, check_schedule, count_errors_device, decode_entry,
+                       draw_symbols, leading_dim, syndrome_device)
 
 MODES = ("softening", "direct", "hard")
 STREAMS = ("torch", "numpy")
@@ -105,8 +105,9 @@ def llr_source(nm: NoiseMapper, pa: PAMAlphabet, S: int, B: int, gen, mode: str 
 class Simulator:
     def __init__(self, decoder: Decoder, bps: int, mode: str = "softening", max_iterations: int = 50,
                  alpha: float = 1.0, batch: int = 4096, configuration_base: bool = False, step: float = 2.0,
-                 device: int = 0, demapper: str = "search", stream: str = "torch"):
+                 device: int = 0, demapper: str = "search", stream: str = "torch", schedule: str = "flooding"):
         self.stream = check_stream(stream)
+        self.schedule = check_schedule(schedule)   # "layered": this library's schedule, not the reference's
         self.demapper = check_demapper(demapper)   # softening mode only; the other modes have no soft demap
         import torch
 
@@ -147,7 +148,7 @@ class Simulator:
         lappr, synd, word, ld = self.frames(nm, B, gen, two_var)
         if hook is not None:
             hook(lappr, synd, word, B)
-        fin, succ, its = self.dec.decode_device(lappr, synd, B, self.max_iterations)
+        fin, succ, its = decode_entry(self.dec, self.schedule)(lappr, synd, B, self.max_iterations)
         ferr = torch.empty(B, dtype=torch.int32, device=self.device)
         delta = torch.zeros(5, dtype=torch.int64, device=self.device)
         count_errors_device(False, B, ld, self.K, fin, word, succ, its, ferr, delta)
@@ -158,7 +159,9 @@ class Simulator:
         (snr_dB, ber, fer, avg_iterations_of_successes).  hook(batch_index, lappr, synd, word, B):
         optional view of every shard's inputs (tests).  With stream="numpy" the frames come from
         numpy's global stream, which is left after the last frame counted; `seed` is not read (the
-        caller seeds numpy, as for montecarlo_information)."""
+        caller seeds numpy, as for montecarlo_information).  With schedule="layered" the frames are
+        the same (stream="numpy": still the reference's frames), but the decoder is this library's
+        layered one, so the returned tuple is NOT the reference's."""
         Es = self.pa.variance
         two_var = Es * (10 ** (-snr_dB / 10))          # reconciliation.pyx:191-192, 272-273
         N0 = Es * (10 ** (-snr_dB / 10)) / 2           # reconciliation.pyx:109-110
@@ -316,24 +319,30 @@ def run_numpy_stream(batch_fn, hook, batch: int, simulation_loops: int, ferr_cou
 
 
 def simulate_softening_snr_dB(snr_dB, dec, bps, nmconfig, decoder_iterations, simulation_loops, ferr_count_min,
-                              alpha=1.0, batch=4096, seed=0, demapper="search", stream="torch"):
+                              alpha=1.0, batch=4096, seed=0, demapper="search", stream="torch",
+                              schedule="flooding"):
     """reconciliation.pyx:93-168 (the Matrix is the decoder's own graph).  demapper="simplified"
     swaps demap_lappr_array (:143) for demap_lappr_simplified_array.  stream="numpy": after
-    np.random.seed(s), the tuple the reference returns after that seed (`seed` is not read)."""
-    sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch, demapper=demapper, stream=stream)
+    np.random.seed(s), the tuple the reference returns after that seed (`seed` is not read).
+    schedule="layered" decodes with the layered schedule (Decoder.decode_layered_device): with
+    stream="numpy" the frames are still the reference's, but the returned tuple is not."""
+    sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch, demapper=demapper, stream=stream,
+                    schedule=schedule)
     sim.cfg = np.ascontiguousarray(nmconfig, np.uint8)
     return sim.run_snr(snr_dB, simulation_loops, ferr_count_min, seed)
 
 
 def simulate_direct_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096, seed=0,
-                           stream="torch"):
-    """reconciliation.pyx:173-249"""
-    return Simulator(dec, bps, "direct", decoder_iterations, 1.0, batch, stream=stream).run_snr(
+                           stream="torch", schedule="flooding"):
+    """reconciliation.pyx:173-249.  schedule="layered": the layered decode; with stream="numpy" the
+    frames are still the reference's, but the returned tuple is not."""
+    return Simulator(dec, bps, "direct", decoder_iterations, 1.0, batch, stream=stream, schedule=schedule).run_snr(
         snr_dB, simulation_loops, ferr_count_min, seed)
 
 
 def simulate_hard_reverse_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096,
-                                 seed=0, stream="torch"):
-    """reconciliation.pyx:253-329"""
-    return Simulator(dec, bps, "hard", decoder_iterations, 1.0, batch, stream=stream).run_snr(
+                                 seed=0, stream="torch", schedule="flooding"):
+    """reconciliation.pyx:253-329.  schedule="layered": the layered decode; with stream="numpy" the
+    frames are still the reference's, but the returned tuple is not."""
+    return Simulator(dec, bps, "hard", decoder_iterations, 1.0, batch, stream=stream, schedule=schedule).run_snr(
         snr_dB, simulation_loops, ferr_count_min, seed)

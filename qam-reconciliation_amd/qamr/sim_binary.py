@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import dptr, stream_arg
 from .decoder import Decoder
-from .pipeline import count_errors_device, leading_dim, syndrome_device
+from .pipeline import check_schedule, count_errors_device, decode_entry, leading_dim, syndrome_device
 from .sim import StopRule, run_seeded
 
 CHANNELS = ("biawgn", "biawgn_hard", "bsc")
@@ -69,8 +69,9 @@ def bsc_coefficient(rber: float) -> float:
 
 class BinaryChannelSimulator:
     def __init__(self, decoder: Decoder, channel: str, max_iterations: int = 30, alpha: float = 1.0,
-                 batch: int = 4096, device: int = 0):
+                 batch: int = 4096, device: int = 0, schedule: str = "flooding"):
         self.channel = check_channel(channel)
+        self.schedule = check_schedule(schedule)   # "layered": Decoder.decode_layered_device
         import torch
 
         self.dec = decoder
@@ -115,7 +116,7 @@ class BinaryChannelSimulator:
         llr, synd, word, ld = self.frames(point, B, gen)
         if hook is not None:
             hook(llr, synd, word, B)
-        fin, succ, its = self.dec.decode_device(llr, synd, B, self.max_iterations)
+        fin, succ, its = decode_entry(self.dec, self.schedule)(llr, synd, B, self.max_iterations)
         ferr = torch.empty(B, dtype=torch.int32, device=self.device)
         delta = torch.zeros(5, dtype=torch.int64, device=self.device)
         count_errors_device(True, B, ld, self.K, fin, word, succ, its, ferr, delta)

@@ -3,7 +3,7 @@ sims/sim_bsc.py (arguments of sim_bsc.py:10-28, CSV of :85-89).
 
     PYTHONPATH=qam-reconciliation_amd python -m qamr.sim_bsc EDGEFILE \\
         [--out out.csv] [--maxiter 30] [--minerr 20] [--simloops 30] [--rber 0.01 0.04] \\
-        [--rpoints 31] [--batch 4096] [--seed 0]
+        [--rpoints 31] [--batch 4096] [--seed 0] [--schedule {flooding,layered}]
 """
 from __future__ import annotations
 
@@ -28,6 +28,9 @@ def build_parser():
     p.add_argument("--rpoints", type=int, default=31, help="Number of equally spaced raw-BER points")
     p.add_argument("--batch", type=int, default=4096, help="frames per GPU per batch")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--schedule", choices=("flooding", "layered"), default="flooding",
+                   help="Decode schedule: the reference's flooding one, or the layered (serial-check) one of this "
+                        "library, which needs about half the iterations (its LAPPRs and iteration counts differ)")
     return p
 
 

@@ -3,7 +3,7 @@ sims/sim_decode.py (arguments of sim_decode.py:13-33, CSV of :127-133).
 
     PYTHONPATH=qam-reconciliation_amd python -m qamr.sim_decode EDGEFILE \\
         [--out out.csv] [--maxiter 30] [--minerr 20] [--simloops 30] [--snr 0 5] [--nsnr 11] \\
-        [--alpha 1.0] [--hard] [--batch 4096] [--seed 0]
+        [--alpha 1.0] [--hard] [--batch 4096] [--seed 0] [--schedule {flooding,layered}]
 
 Instead of one OS process per point (parfor), every point runs batched on the GPU(s); launched
 under torchrun, each rank takes its share of every batch (qamr.sim_binary, qamr.dist).
@@ -32,6 +32,9 @@ def build_parser(prog: str = "sim_decode"):
     p.add_argument("--hard", action="store_true", default=False, help="Hard-decide the channel output")
     p.add_argument("--batch", type=int, default=4096, help="frames per GPU per batch")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--schedule", choices=("flooding", "layered"), default="flooding",
+                   help="Decode schedule: the reference's flooding one, or the layered (serial-check) one of this "
+                        "library, which needs about half the iterations (its LAPPRs and iteration counts differ)")
     return p
 
 
@@ -54,7 +57,8 @@ def sweep(args, channel: str, points, column: str):
     world, rank, local = dist.init()
     vid, cid = load_edge_csv(args.edgefile)  # counts row skipped (sim_decode.py:52-53: vid[1:])
     dec = Decoder(vid, cid, device=local)
-    sim = BinaryChannelSimulator(dec, channel, args.maxiter, getattr(args, "alpha", 1.0), args.batch, device=local)
+    sim = BinaryChannelSimulator(dec, channel, args.maxiter, getattr(args, "alpha", 1.0), args.batch, device=local,
+                                 schedule=args.schedule)
     rows = []
     for x in points:
         rows.append(sim.run_point(float(x), args.simloops, args.minerr, args.seed))

@@ -5,7 +5,7 @@ CSV schema of sim_reconciliation.py:27-102, README.md:107-145).
         [--out out.csv] [--maxiter 50] [--ferr-count-min 100] [--alpha 1.0] \\
         [--simloops 5000] [--snr 0 5] [--nsnr 11] [--bps 2] [--hard | --direct] \\
         [--configuration-base] [--batch 4096] [--seed 0] [--demapper {search,simplified}] \\
-        [--stream {torch,numpy}]
+        [--stream {torch,numpy}] [--schedule {flooding,layered}]
 
 Instead of one OS process per SNR point (parfor), every SNR point runs batched
 on the GPU(s); launched under torchrun, each rank takes its share of every
@@ -43,6 +43,9 @@ def build_parser():
                    help="RNG stream of the frames: torch's generator (seeded per seed, rank and batch), or numpy's "
                         "legacy global stream, seeded with --seed before every SNR point: each row is then what "
                         "the reference's function returns after np.random.seed(seed) (one rank only)")
+    p.add_argument("--schedule", choices=("flooding", "layered"), default="flooding",
+                   help="Decode schedule: the reference's flooding one, or the layered (serial-check) one of this "
+                        "library, which needs about half the iterations (its LAPPRs and iteration counts differ)")
     return p
 
 
@@ -60,7 +63,7 @@ def main(argv=None):
     mode = "direct" if args.direct else ("hard" if args.hard else "softening")
     sim = Simulator(dec, args.bps, mode, args.maxiter, args.alpha, args.batch,
                     configuration_base=args.configuration_base, device=local, demapper=args.demapper,
-                    stream=args.stream)
+                    stream=args.stream, schedule=args.schedule)
     rows = []
     for snr in np.linspace(args.snr[0], args.snr[1], args.nsnr):
         if args.stream == "numpy":
