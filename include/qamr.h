@@ -394,6 +394,71 @@ QR_API int qr_lappr_info_device(int32_t bit_per_symbol, int32_t B, int32_t ld, i
 QR_API int qr_lappr_info_host(int32_t device, int32_t bit_per_symbol, int64_t S, const double *lappr,
                               const uint8_t *word, int32_t A, const double *alphas, double *loss, int64_t *errors);
 
+/* ------------------------------ sampled density evolution of a code ensemble */
+/* Whether a degree distribution decodes an empirical LLR density (the softened LAPPRs at a scale
+ * alpha, say) within T iterations: the decoder's arithmetic applied to random draws from populations of
+ * M messages instead of to a graph.  Not a reference interface; the definition is this library's and the
+ * results are bit-exact against it.  All arithmetic is IEEE fp64, every operation rounded separately (no
+ * FMA), exp and log glibc's as in the decoder.
+ *
+ * Random indices, counter-based (uint64, wrapping):
+ *   mix(x):  x = (x ^ x>>30) * 0xBF58476D1CE4E5B9;  x = (x ^ x>>27) * 0x94D049BB133111EB;  return x ^ x>>31
+ *   ctr(t, phase, j, k) = ((t*4 + phase) * 2^32 + j) * 512 + k
+ *   z = mix(seed + 0x9E3779B97F4A7C15 * (ctr + 1))
+ *   rnd(t, phase, j, k, n) = ((z >> 32) * n) >> 32            for 1 <= n < 2^31
+ * (with seed 0, ctr = 0, 1, 2 give SplitMix64's first outputs 0xE220A8397B1DCDAF, 0x6E789E6AA1B965F4,
+ * 0x06C45D188009454F).
+ *
+ * Inputs: a channel population u[Mu] of signed LAPPRs (u > 0: correct); the ensemble's degree tables
+ * edge_vdeg[Ne], edge_cdeg[Ne] (per edge of a multiset of edges, the degree of its variable and of its
+ * check: the edge perspective) and node_vdeg[Nv] (per variable: the node perspective; 0 is an isolated
+ * variable); the population size M, the iterations T, a 64-bit seed.  Variable degrees 1..255 (node_vdeg
+ * 0..255), check degrees 2..255; Mu, Ne, Nv in [1, 2^31), M in [1, 2^30], T in [0, 10000].
+ *
+ * c2v(0)[j] = +0.0 for every j.  For t = 1..T and every j in [0, M):
+ *   phase 0 (variable):  d = edge_vdeg[rnd(t,0,j,0,Ne)];   s = u[rnd(t,0,j,1,Mu)]
+ *                        for k = 0 .. d-2 ascending:  s = s + c2v(t-1)[rnd(t,0,j,2+k,M)]
+ *                        v2c(t)[j] = s
+ *   phase 1 (check):     d = edge_cdeg[rnd(t,1,j,0,Ne)];   F = v2c(t)[rnd(t,1,j,2,M)]
+ *                        for k = 1 .. d-2 ascending:  F = box_plus(F, v2c(t)[rnd(t,1,j,2+k,M)])
+ *                        c2v(t)[j] = F
+ * box_plus is the reference's (decoder.pyx:41-45) in its operand order, F the first operand; no syndrome
+ * sign (the population is already signed).  For t = 0..T, phase 2 is the decision of
+ * count_errors_from_lappr (lappr >= 0 is correct; NaN counts as an error):
+ *   d = node_vdeg[rnd(t,2,j,0,Nv)];   p = u[rnd(t,2,j,1,Mu)]
+ *   for k = 0 .. d-1 ascending:  p = p + c2v(t)[rnd(t,2,j,2+k,M)]
+ *   errors[t] = #{ j : !(p >= 0) }
+ * Outputs: errors[T+1] int64 and the populations v2c(T)[M], c2v(T)[M]; for T = 0 v2c is not written and
+ * c2v is all +0.0.
+ *
+ * Limitation: the bit levels are mixed i.i.d. over the variables (the usual BICM approximation); which
+ * level sits on which variable of an irregular code is not modelled. */
+typedef struct qr_de_tables qr_de_tables; /* an ensemble's three degree tables in HBM */
+/* The tables from host arrays: every degree validated on the host (QR_EVALUE: Ne or Nv outside [1, 2^31),
+ * a variable degree outside 1..255, a node degree outside 0..255, a check degree outside 2..255, a null
+ * pointer; all before any device call), uploaded once to GPU `device`. */
+QR_API int qr_de_tables_create(int32_t device, int64_t Ne, const int32_t *edge_vdeg, const int32_t *edge_cdeg,
+                               int64_t Nv, const int32_t *node_vdeg, qr_de_tables **out);
+QR_API int qr_de_tables_destroy(qr_de_tables *tables);
+/* Signed population from a batch: for row r and frame f < B of the decoder's frame-innermost [rows][ld]
+ * arrays, x = alpha * d_lappr[r][f] (one rounding) and d_u[r * B + f] = x where d_word[r][f] == 0, x with
+ * its sign bit flipped otherwise (NaN keeps its payload).  The padding columns [B, ld) are not read.
+ * QR_EVALUE: B < 1, B > ld, ld % 64 != 0, rows < 1, rows * B >= 2^31, an alpha that is not finite, a null
+ * pointer.  One launch on `stream` of the current device, asynchronous. */
+QR_API int qr_de_population_device(int32_t B, int32_t ld, int64_t rows, const double *d_lappr, const uint8_t *d_word,
+                                   double alpha, double *d_u, void *stream);
+/* The evolution above on the tables' device: d_u [Mu], d_v2c [M], d_c2v [M] fp64, d_errors [T+1] int64.
+ * It clears d_c2v and d_errors (hipMemsetAsync), then 1 + 3T launches on `stream`; asynchronous, no
+ * allocation, no workspace, capturable into a graph.  QR_EVALUE, before any launch and with no output
+ * written: Mu outside [1, 2^31), M outside [1, 2^30], T outside [0, 10000], a null pointer. */
+QR_API int qr_de_evolve_device(const qr_de_tables *tables, int64_t Mu, const double *d_u, int64_t M, int32_t T,
+                               uint64_t seed, double *d_v2c, double *d_c2v, int64_t *d_errors, void *stream);
+/* The same from host arrays on GPU `device` (the tables as qr_de_tables_create takes them): synchronous
+ * copies around qr_de_evolve_device, for one-off use and tests.  v2c is left alone when T == 0. */
+QR_API int qr_de_evolve_host(int32_t device, int64_t Ne, const int32_t *edge_vdeg, const int32_t *edge_cdeg, int64_t Nv,
+                             const int32_t *node_vdeg, int64_t Mu, const double *u, int64_t M, int32_t T, uint64_t seed,
+                             double *v2c, double *c2v, int64_t *errors);
+
 /* The arithmetic primitives of the bit-exact paths (glibc exp / log, the box-plus built from them,
  * cephes erf, the demapper's division by 2 sigma^2), evaluated on the device element by element:
  * out[k] = fn(a[k]) or fn(a[k], b[k]), host arrays of n elements, synchronous, on the caller's current

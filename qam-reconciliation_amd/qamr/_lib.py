@@ -74,6 +74,11 @@ SIGNATURES = {
     "qr_lappr_info_workspace_size": [i32, i32, i64, i32, P(C.c_size_t)],
     "qr_lappr_info_device": [i32, i32, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp],
     "qr_lappr_info_host": [i32, i32, i64, vp, vp, i32, vp, vp, vp],
+    "qr_de_tables_create": [i32, i64, vp, vp, i64, vp, P(vp)],
+    "qr_de_tables_destroy": [vp],
+    "qr_de_population_device": [i32, i32, i64, vp, vp, f64, vp, vp],
+    "qr_de_evolve_device": [vp, i64, vp, i64, i32, C.c_uint64, vp, vp, vp, vp],
+    "qr_de_evolve_host": [i32, i64, vp, vp, i64, vp, i64, vp, i64, i32, C.c_uint64, vp, vp, vp],
     "qr_math_eval_host": [i32, i32, i64, vp, vp, vp],
     "qr_mi_quad_batch": [vp, vp, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp],
     "qr_mi_quad_stats": [vp],

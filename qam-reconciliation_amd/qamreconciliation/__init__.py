@@ -11,5 +11,5 @@ from .decoder import Decoder  # noqa: F401
 from .matrix import Matrix  # noqa: F401
 from .noisemapper import NoiseMapper, NoiseDemapper, NoiseMapperFlipSign, NoiseMapperAntiFlipSign  # noqa: F401
 from .alphabet import PAMAlphabet  # noqa: F401
-from . import alphabet, bicm, decoder, matrix, mutual_information, noisemapper, utils  # noqa: F401
+from . import alphabet, bicm, decoder, density_evolution, matrix, mutual_information, noisemapper, utils  # noqa: F401
 from .utils import count_errors_from_lappr  # noqa: F401
