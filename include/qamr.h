@@ -595,6 +595,42 @@ QR_API int qr_count_errors_device(int32_t B, int32_t ld, int64_t K, const double
                            const uint8_t *d_success, const int32_t *d_iters, int32_t *d_frame_errors,
                            int64_t *d_counters, void *stream);
 
+/* ------------------------------------------------------- rate adaptation */
+/* Rate adaptation of one mother code (puncturing, shortening, blind rounds).  Not a reference
+ * interface: the definition is this library's (qamr/rate_adapt.py expand_host states it on the host).
+ * Of the V variables, n carry the payload, s are shortened and p are punctured; d_slot int32[V] says
+ * which: d_slot[v] = k >= 0 makes v payload row k (0 <= k < n), d_slot[v] = -1 - j makes it filler j
+ * (j < s shortened, s <= j < s + p punctured).  With the frame-innermost d_lappr_pay [n][ld],
+ * d_word_pay [n][ld], d_fill [p + s][ld] (bits, any non-zero byte is 1) and d_revealed_or_null
+ * int32[ld] (absent: 0 for every frame), for every frame f < B:
+ *   payload row k : d_lappr[v][f] = d_lappr_pay[k][f] and d_word[v][f] = d_word_pay[k][f], bit for
+ *                   bit (NaN payloads, +-inf and -0.0 are kept);
+ *   filler j      : d_word[v][f] = d_fill[j][f] != 0; the filler is known iff
+ *                   j < s + max(d_revealed[f], 0) (any count >= p discloses everything); a known filler
+ *                   takes +L for bit 0 and -L for bit 1, an unknown one +0.0.
+ * L is the LAPPR of a disclosed bit and must be finite: box_plus(inf, inf) is NaN in the reference's
+ * arithmetic (|a - b| is NaN), and a decode with +-inf at the shortened positions returns NaN for
+ * every LAPPR of every frame.  QR_SHORTENED_LAPPR = 1e300 is the value the reference itself uses for
+ * a certain bit (noisemapper.pyx:218), and box_plus(1e300, 1e300) is 1e300.
+ * One launch on `stream`, asynchronous, allocates nothing, capturable; only columns [0, B) of
+ * d_lappr [V][ld] and d_word [V][ld] are written.  The LAPPR arrays must be 16-byte aligned, the bit
+ * arrays 8-byte aligned.  QR_EVALUE before the device is touched: a null pointer (other than
+ * d_revealed_or_null), a misaligned array, B < 1, B > ld, ld % 64 != 0, n + p + s != V, n < 1, p < 0,
+ * s < 0, L not finite or <= 0. */
+#define QR_SHORTENED_LAPPR 1e300
+QR_API int qr_rate_adapt_expand_device(int64_t V, int64_t n, int64_t p, int64_t s, const int32_t *d_slot, int32_t B,
+                                       int32_t ld, const double *d_lappr_pay, const uint8_t *d_word_pay,
+                                       const uint8_t *d_fill, const int32_t *d_revealed_or_null, double L,
+                                       double *d_lappr, uint8_t *d_word, void *stream);
+/* qr_count_errors_device over the rows d_rows int32[n_rows] of the [V][ld] arrays in place of the
+ * first K (a rate-adapted frame's payload rows): the same decision rule (utils.pyx:27-40: a NaN
+ * decides 1), per-frame counts and five counters, accumulated the same way; with d_rows = 0..K-1 its
+ * outputs are qr_count_errors_device's.  QR_EVALUE for a null pointer, a bad B / ld, n_rows < 0. */
+QR_API int qr_count_errors_rows_device(int32_t B, int32_t ld, int64_t n_rows, const int32_t *d_rows,
+                                       const double *d_final, const uint8_t *d_word, const uint8_t *d_success,
+                                       const int32_t *d_iters, int32_t *d_frame_errors, int64_t *d_counters,
+                                       void *stream);
+
 /* ------------------------------------ code evaluation on a binary channel */
 /* The decoder's input of sims/sim_decode.py and sims/sim_direct.py, frame-innermost:
  * d_word[V][ld] (bits), d_z[V][ld] (standard normal draws) -> d_llr[V][ld], columns [0, B) only.

@@ -12,7 +12,8 @@
 // tests/test_host_logic.py).  The site numbers are one list across the units: 1..9 and 17..19 the
 // decoder's units (decode_dev.hpp DebugSite), 10..11 grid_interp.hpp (GridDebugSite), 12..16 mi.hip
 // (MiDebugSite), 20..24 npstream.hip (NpDebugSite), 25..26 lappr_info.hip (InfoDebugSite), 27..30 decode_layered.hip
-// (decode_dev.hpp DebugSite), 31..34 density_evolution.hip (DeDebugSite).
+// (decode_dev.hpp DebugSite), 31..34 density_evolution.hip (DeDebugSite),
+// 35..38 rate_adapt.hip (RaDebugSite).
 #pragma once
 #include <hip/hip_runtime.h>
 

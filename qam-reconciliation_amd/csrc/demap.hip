@@ -389,6 +389,14 @@ int launch_count_errors(bool neg, int B, int ld, int64_t K, const double *d_fina
     return QR_OK;
 }
 
+// k_count_finish alone, for a unit that counts the frame errors itself (rate_adapt.hip)
+int launch_count_finish(int B, const int32_t *ferr, const uint8_t *d_success, const int32_t *d_iters, int64_t *d_counters,
+                        hipStream_t s) {
+    k_count_finish<<<(B + 255) / 256, 256, 0, s>>>(B, ferr, d_success, d_iters, (unsigned long long *)d_counters);
+    QR_LAUNCH_CHECK();
+    return QR_OK;
+}
+
 int check_shape(int B, int ld, int64_t S) {
     if (B <= 0 || ld < B || ld % kWave) return set_error(QR_EVALUE, "need 0 < B <= ld, ld %% 64 == 0 (B=%d ld=%d)", B, ld);
     if (S <= 0) return set_error(QR_EVALUE, "S must be positive");

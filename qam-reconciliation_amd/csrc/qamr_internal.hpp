@@ -117,6 +117,9 @@ unsigned demap_wave_grid(int device, int64_t items);      // demap.hip: workgrou
 int launch_count_errors(bool neg, int B, int ld, int64_t K, const double *d_final, const uint8_t *d_word,
                         const uint8_t *d_success, const int32_t *d_iters, int32_t *ferr, int64_t *d_counters,
                         hipStream_t s);
+// demap.hip: its second launch alone (ferr[B] -> the five counters), for rate_adapt.hip's row-listed count
+int launch_count_finish(int B, const int32_t *ferr, const uint8_t *d_success, const int32_t *d_iters, int64_t *d_counters,
+                        hipStream_t s);
 struct GridView;                                          // grid_interp.hpp
 GridView grid_view(const qr_demap *dm);                   // demap_interp.hip: the handle's grid, as the kernels take it
 bool grid_fast(const qr_demap *dm);                       // demap_interp.hip: body (b) of the grid's index search

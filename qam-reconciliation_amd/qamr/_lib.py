@@ -93,6 +93,8 @@ SIGNATURES = {
     "qr_direct_lappr_device": [vp, f64, i32, i32, i64, vp, vp, vp],
     "qr_bare_llr_device": [i32, vp, i32, i32, i64, vp, vp, vp],
     "qr_count_errors_device": [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp],
+    "qr_rate_adapt_expand_device": [i64, i64, i64, i64, vp, i32, i32, vp, vp, vp, vp, f64, vp, vp, vp],
+    "qr_count_errors_rows_device": [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
     "qr_biawgn_llr_device": [i32, f64, f64, i32, i32, i64, vp, vp, vp, vp],
     "qr_bsc_llr_device": [f64, f64, i32, i32, i64, vp, vp, vp, vp, vp],
     "qr_count_errors_neg_device": [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp],

@@ -21,6 +21,10 @@ per seed, rank and batch; ``stream="numpy"`` draws the frames from numpy's legac
 the GPU (qamr.npstream), frame after frame as the reference's loop does, so that after
 ``np.random.seed(s)`` the returned tuple is the reference's and ``np.random.get_state()`` is left
 where the reference leaves it (one rank only: the frames of one stream are sequential).
+Rate adaptation (``adapt=RateAdaption(...)``, qamr.rate_adapt; this library's, not the reference's):
+only the n = V - p - s payload variables are drawn from the channel, n / bps symbols; the p punctured
+and s shortened variables are filled with random bits drawn after them, and the bit errors are counted
+over the payload rows (BER over n bits per frame).  torch's stream only.
 """
 from __future__ import annotations
 
@@ -105,8 +109,11 @@ def llr_source(nm: NoiseMapper, pa: PAMAlphabet, S: int, B: int, gen, mode: str 
 class Simulator:
     def __init__(self, decoder: Decoder, bps: int, mode: str = "softening", max_iterations: int = 50,
                  alpha: float = 1.0, batch: int = 4096, configuration_base: bool = False, step: float = 2.0,
-                 device: int = 0, demapper: str = "search", stream: str = "torch", schedule: str = "flooding"):
+                 device: int = 0, demapper: str = "search", stream: str = "torch", schedule: str = "flooding",
+                 adapt=None):
         self.stream = check_stream(stream)
+        if adapt is not None and self.stream == "numpy":
+            raise ValueError('adapt needs stream="torch": the reference\'s stream has no draws for the filler bits')
         self.schedule = check_schedule(schedule)   # "layered": this library's schedule, not the reference's
         self.demapper = check_demapper(demapper)   # softening mode only; the other modes have no soft demap
         import torch
@@ -120,10 +127,17 @@ class Simulator:
         self.alpha = float(alpha)
         self.batch = int(batch)
         self.V, self.C = decoder.vnum, decoder.cnum
-        if self.V % bps:
+        if self.V % bps and adapt is None:   # with an adaptation the payload must be whole symbols, not V
             raise ValueError(f"V={self.V} is not a multiple of bit_per_symbol={bps}")
         self.S = self.V // bps
         self.K = self.V - self.C  # reconciliation.pyx:120-121
+        self.adapt = adapt        # qamr.rate_adapt.RateAdaption: the payload is S' = n / bps symbols
+        self.ber_bits = self.K    # the bits per frame the BER is over: the first K, or the payload's n
+        if adapt is not None:
+            if adapt.V != self.V:
+                raise ValueError(f"the adaptation is for V={adapt.V}, the code has V={self.V}")
+            self.S_pay = adapt.check_bps(bps)
+            self.ber_bits = adapt.n
         self.cfg = np.zeros(self.pa.order, np.uint8) if configuration_base else alternating_config(self.pa.order)
         self.device = torch.device("cuda", device)
         self._dev_index = device
@@ -134,10 +148,26 @@ class Simulator:
         """One batch of inputs for the selected mode: (lappr [V, ld], synd [C, ld], word [V, ld], ld).
         gen: a torch generator, or the NumpyStream the frames are drawn from (stream="numpy")."""
         ld = leading_dim(B)
-        lappr, word = llr_source(nm, self.pa, self.S, B, gen, self.mode, self.demapper, self.alpha, two_variance,
-                                 self.stream, self._tables)
+        if self.adapt is not None:
+            lappr, word = self.adapt.expand_device(*self.payload(nm, B, gen, two_variance)[:3], B)
+        else:
+            lappr, word = llr_source(nm, self.pa, self.S, B, gen, self.mode, self.demapper, self.alpha, two_variance,
+                                     self.stream, self._tables)
         synd = syndrome_device(self.dec, word, B, ld)
         return lappr, synd, word, ld
+
+    def payload(self, nm: NoiseMapper, B: int, gen, two_variance: float):
+        """With an adaptation, what a batch is expanded from: (lappr_pay [n, ld], word_pay [n, ld],
+        fill uint8 [p + s, ld], ld).  The n / bps payload symbols go through the unchanged llr_source;
+        the filler bits are drawn after them."""
+        import torch
+
+        ld = leading_dim(B)
+        lappr_pay, word_pay = llr_source(nm, self.pa, self.S_pay, B, gen, self.mode, self.demapper, self.alpha,
+                                         two_variance, self.stream, self._tables)
+        fill = torch.randint(0, 2, (self.adapt.p + self.adapt.s, ld), dtype=torch.uint8, generator=gen,
+                             device=self.device)
+        return lappr_pay, word_pay, fill, ld
 
     # ------------------------------------------------------------------ run
     def batch_results(self, nm: NoiseMapper, B: int, gen, two_var: float, hook=None):
@@ -151,7 +181,10 @@ class Simulator:
         fin, succ, its = decode_entry(self.dec, self.schedule)(lappr, synd, B, self.max_iterations)
         ferr = torch.empty(B, dtype=torch.int32, device=self.device)
         delta = torch.zeros(5, dtype=torch.int64, device=self.device)
-        count_errors_device(False, B, ld, self.K, fin, word, succ, its, ferr, delta)
+        if self.adapt is not None:
+            self.adapt.count_errors_device(B, ld, fin, word, succ, its, ferr, delta)
+        else:
+            count_errors_device(False, B, ld, self.K, fin, word, succ, its, ferr, delta)
         return ferr, succ[:B], its[:B], delta
 
     def run_snr(self, snr_dB: float, simulation_loops: int, ferr_count_min: int, seed: int = 0, hook=None):
@@ -175,7 +208,7 @@ class Simulator:
         else:
             be, fe, su, it, fr = run_seeded(batch_fn, seed, hook, self.batch, simulation_loops, ferr_count_min,
                                             self.device)
-        return (snr_dB, be / (fr * self.K), fe / fr, 0 if su == 0 else it / su)
+        return (snr_dB, be / (fr * self.ber_bits), fe / fr, 0 if su == 0 else it / su)
 
 
 def shard_counters(ferr, succ, its, n: int):
@@ -320,29 +353,32 @@ def run_numpy_stream(batch_fn, hook, batch: int, simulation_loops: int, ferr_cou
 
 def simulate_softening_snr_dB(snr_dB, dec, bps, nmconfig, decoder_iterations, simulation_loops, ferr_count_min,
                               alpha=1.0, batch=4096, seed=0, demapper="search", stream="torch",
-                              schedule="flooding"):
+                              schedule="flooding", adapt=None):
     """reconciliation.pyx:93-168 (the Matrix is the decoder's own graph).  demapper="simplified"
     swaps demap_lappr_array (:143) for demap_lappr_simplified_array.  stream="numpy": after
     np.random.seed(s), the tuple the reference returns after that seed (`seed` is not read).
     schedule="layered" decodes with the layered schedule (Decoder.decode_layered_device): with
-    stream="numpy" the frames are still the reference's, but the returned tuple is not."""
+    stream="numpy" the frames are still the reference's, but the returned tuple is not.
+    adapt: a qamr.rate_adapt.RateAdaption (puncturing / shortening; stream="torch" only)."""
     sim = Simulator(dec, bps, "softening", decoder_iterations, alpha, batch, demapper=demapper, stream=stream,
-                    schedule=schedule)
+                    schedule=schedule, adapt=adapt)
     sim.cfg = np.ascontiguousarray(nmconfig, np.uint8)
     return sim.run_snr(snr_dB, simulation_loops, ferr_count_min, seed)
 
 
 def simulate_direct_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096, seed=0,
-                           stream="torch", schedule="flooding"):
+                           stream="torch", schedule="flooding", adapt=None):
     """reconciliation.pyx:173-249.  schedule="layered": the layered decode; with stream="numpy" the
     frames are still the reference's, but the returned tuple is not."""
-    return Simulator(dec, bps, "direct", decoder_iterations, 1.0, batch, stream=stream, schedule=schedule).run_snr(
+    return Simulator(dec, bps, "direct", decoder_iterations, 1.0, batch, stream=stream, schedule=schedule,
+                     adapt=adapt).run_snr(
         snr_dB, simulation_loops, ferr_count_min, seed)
 
 
 def simulate_hard_reverse_snr_dB(snr_dB, dec, bps, decoder_iterations, simulation_loops, ferr_count_min, batch=4096,
-                                 seed=0, stream="torch", schedule="flooding"):
+                                 seed=0, stream="torch", schedule="flooding", adapt=None):
     """reconciliation.pyx:253-329.  schedule="layered": the layered decode; with stream="numpy" the
     frames are still the reference's, but the returned tuple is not."""
-    return Simulator(dec, bps, "hard", decoder_iterations, 1.0, batch, stream=stream, schedule=schedule).run_snr(
+    return Simulator(dec, bps, "hard", decoder_iterations, 1.0, batch, stream=stream, schedule=schedule,
+                     adapt=adapt).run_snr(
         snr_dB, simulation_loops, ferr_count_min, seed)

@@ -5,7 +5,8 @@ CSV schema of sim_reconciliation.py:27-102, README.md:107-145).
         [--out out.csv] [--maxiter 50] [--ferr-count-min 100] [--alpha 1.0] \\
         [--simloops 5000] [--snr 0 5] [--nsnr 11] [--bps 2] [--hard | --direct] \\
         [--configuration-base] [--batch 4096] [--seed 0] [--demapper {search,simplified}] \\
-        [--stream {torch,numpy}] [--schedule {flooding,layered}]
+        [--stream {torch,numpy}] [--schedule {flooding,layered}] \\
+        [--punctured P --shortened S --adapt-seed Q]
 
 Instead of one OS process per SNR point (parfor), every SNR point runs batched
 on the GPU(s); launched under torchrun, each rank takes its share of every
@@ -46,7 +47,32 @@ def build_parser():
     p.add_argument("--schedule", choices=("flooding", "layered"), default="flooding",
                    help="Decode schedule: the reference's flooding one, or the layered (serial-check) one of this "
                         "library, which needs about half the iterations (its LAPPRs and iteration counts differ)")
+    p.add_argument("--punctured", type=int, default=0, metavar="P",
+                   help="Rate adaptation (this library's): P variables carry undisclosed random bits, the rate goes up")
+    p.add_argument("--shortened", type=int, default=0, metavar="S",
+                   help="Rate adaptation: S variables carry disclosed random bits, the rate goes down")
+    p.add_argument("--adapt-seed", type=int, default=0, metavar="Q",
+                   help="Seed of the walk that orders the variables (qamr.rate_adapt.untainted_order)")
     return p
+
+
+def adaption_from_args(vid, cid, punctured: int, shortened: int, adapt_seed: int, report: bool = True):
+    """The RateAdaption of --punctured / --shortened / --adapt-seed (None when both are 0); prints one
+    line with the rate, and warns when more variables are punctured than the walk found untainted."""
+    if not (punctured or shortened):
+        return None
+    from .rate_adapt import RateAdaption, untainted_order
+
+    order, u = untainted_order(vid, cid, adapt_seed)
+    adapt = RateAdaption.from_order(order, punctured, shortened)
+    if report:
+        K = adapt.V - (int(np.max(cid)) + 1)
+        print(f"rate adaptation: p={adapt.p} s={adapt.s} payload n={adapt.n} rate={adapt.rate(K):.6g} "
+              f"(mother code {K / adapt.V:.6g}), untainted u={u}", flush=True)
+        if punctured > u:
+            print(f"warning: --punctured {punctured} > u = {u}: the punctured variables past the first {u} share a "
+                  "check with another one (or repeat one) and may not be recovered", file=sys.stderr, flush=True)
+    return adapt
 
 
 def main(argv=None):
@@ -61,9 +87,10 @@ def main(argv=None):
     vid, cid = load_edge_csv(args.edgefile)  # counts row skipped (sim_reconciliation.py:60)
     dec = Decoder(vid, cid, device=local)
     mode = "direct" if args.direct else ("hard" if args.hard else "softening")
+    adapt = adaption_from_args(vid, cid, args.punctured, args.shortened, args.adapt_seed, report=rank == 0)
     sim = Simulator(dec, args.bps, mode, args.maxiter, args.alpha, args.batch,
                     configuration_base=args.configuration_base, device=local, demapper=args.demapper,
-                    stream=args.stream, schedule=args.schedule)
+                    stream=args.stream, schedule=args.schedule, adapt=adapt)
     rows = []
     for snr in np.linspace(args.snr[0], args.snr[1], args.nsnr):
         if args.stream == "numpy":

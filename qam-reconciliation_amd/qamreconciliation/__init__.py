@@ -11,5 +11,6 @@ from .decoder import Decoder  # noqa: F401
 from .matrix import Matrix  # noqa: F401
 from .noisemapper import NoiseMapper, NoiseDemapper, NoiseMapperFlipSign, NoiseMapperAntiFlipSign  # noqa: F401
 from .alphabet import PAMAlphabet  # noqa: F401
-from . import alphabet, bicm, decoder, density_evolution, matrix, mutual_information, noisemapper, utils  # noqa: F401
+from . import (alphabet, bicm, decoder, density_evolution, matrix, mutual_information, noisemapper,  # noqa: F401
+               rate_adapt, utils)
 from .utils import count_errors_from_lappr  # noqa: F401
